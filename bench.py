@@ -14,6 +14,9 @@ Baseline: the reference's only published number, 3.12 samples/s x 512 tokens = 1
 (ZeRO-2, 1x V100, training/train.ipynb:442).
 
 Usage: python bench.py [--gpus N --steps K --warmup W]   (N>1: under torch.distributed.run)
+A plain run measures the headline figure only.  ``--full`` adds, after the timed steps, the
+partitioned ZeRO-3 schedules, the serving benchmarks, the transport probe and the fixed-work box
+record (``extra.*``); ``--dump-outputs DIR`` writes the last timed step's outputs as .npy files.
 """
 from __future__ import annotations
 
@@ -420,6 +423,40 @@ def _provenance():
         return {"error": repr(e)[:200]}
 
 
+DUMP_SAMPLE = 1 << 22  # adapter elements kept by --dump-outputs (16 MiB as float32)
+
+
+def dump_outputs(out_dir: str, loss, model) -> None:
+    """--dump-outputs: what the last timed optimizer step handed back to its caller, as .npy.
+
+    * ``loss.npy``            float32 [1]: the loss the last timed forward returned;
+    * ``adapter_norms.npy``   float64 [T]: L2 norm of each trainable (adapter) tensor after the
+      last timed step, in ``named_parameters`` order -- every updated element counts;
+    * ``adapter_sample.npy``  float32 [min(n, 2^22)]: the updated adapters, flattened and
+      concatenated in the same order, at positions drawn once from a fixed seed (all of them
+      when there are no more than 2^22).
+    Inputs, weights and dropout masks are seeded, so two builds run with the same arguments
+    can be compared file by file.  On the GPU the adapter gradients are summed with f32 atomics
+    by default, so two runs of one build agree to rounding, not bit for bit (measured on
+    Llama-2-7B after 25 steps: loss within 5e-4, adapters within a few lr-sized AdamW updates);
+    LUMEN_LORA_DETERMINISTIC=1 selects the fixed-order sums."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p.detach() for _, p in model.named_parameters() if p.requires_grad]
+    norms = np.array([float(p.double().norm().item()) for p in params], dtype=np.float64)
+    flat = torch.cat([p.float().reshape(-1) for p in params]).cpu()
+    if flat.numel() > DUMP_SAMPLE:
+        g = torch.Generator(device="cpu").manual_seed(2024)
+        idx = torch.randperm(flat.numel(), generator=g)[:DUMP_SAMPLE].sort().values
+        flat = flat[idx]
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(out_dir, "adapter_norms.npy"), norms)
+    np.save(os.path.join(out_dir, "adapter_sample.npy"), flat.numpy())
+
+
 def _claim_stdout():
     """The driver contract: stdout carries exactly one JSON line.  Keep a private handle on the
     real stdout for it and point fd 1 at stderr, so chatter from native libraries (gloo's
@@ -490,7 +527,20 @@ def main():
                     help="(default, GPU) extra.box: clock / power sampled through the timed "
                          "region plus a fixed 8192^3 GEMM and a 4 GiB HBM read")
     ap.add_argument("--no_box", dest="box", action="store_false")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the sections beyond the headline figure "
+                         "(--serve, --partitioned, --comm_probe, --serve_tp, --box; each still has "
+                         "its own switch).  Without --full none of them runs: the benchmark sets "
+                         "up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned to its "
+                         "caller as DIR/<name>.npy (float32 / float64): the loss, the L2 norm of "
+                         "every adapter tensor and a fixed seeded sample of the updated adapters")
     args = ap.parse_args()
+    if not args.full:
+        args.serve = args.comm_probe = args.box = False
+        args.partitioned = ""
+        args.serve_tp = 0
 
     import torch
     import torch.distributed as dist
@@ -636,7 +686,8 @@ def main():
                   f"{o['section'] if o else 'headline / between sections'}", file=sys.stderr,
                   flush=True)
 
-    _th.Thread(target=_heartbeat, daemon=True, name="bench-heartbeat").start()
+    if args.full:
+        _th.Thread(target=_heartbeat, daemon=True, name="bench-heartbeat").start()
     hwmon = boxcal.gpu_hwmon(env.device) if (on_gpu and args.box) else None
     sampler = boxcal.HwmonSampler(hwmon).start() if (on_gpu and args.box) else None
     # every timed step must really update the adapters: a non-finite gradient makes the fused
@@ -666,6 +717,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt, exposed_ms, peak_gb = (float(x) for x in t.tolist())
     final_loss = float(loss.item())
+    if args.dump_outputs and env.is_main:
+        dump_outputs(args.dump_outputs, loss, model)
     skipped = engine.skipped_steps - sk0
     if skipped and env.is_main:
         print(f"[bench] WARNING: {skipped} of {args.steps} timed optimizer steps were skipped "

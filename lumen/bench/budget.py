@@ -1,7 +1,7 @@
 """One overall wall deadline for bench.py's optional sections (VERDICT r5 "Next" #7).
 
-After the timed headline region bench.py runs optional sections: the transport probe, the two
-partitioned ZeRO-3 schedules, the TP = 1 serving bench (N = 1) or TP = N serving (N > 1).  On a
+After the timed headline region ``bench.py --full`` runs optional sections: the transport probe,
+the two partitioned ZeRO-3 schedules, the TP = 1 serving bench (N = 1) or TP = N serving (N > 1).  On a
 first 8-GPU node their costs are unknown, and the driver kills the whole run at its timeout
 (600 s in every record so far) -- which would lose the headline line too.  ``WallBudget``
 counts every section against one deadline measured from process start, skips a section whose

@@ -320,7 +320,7 @@ def test_bench_contract_torchrun(world):
                           "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port",
                           str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world),
                           "--steps", "2", "--warmup", "1", "--model", "tiny-llama", "--seq_len",
-                          "32", "--micro_batch", "2", "--partitioned_steps", "2"],
+                          "32", "--micro_batch", "2", "--partitioned_steps", "2", "--full"],
                          capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, OMP_NUM_THREADS="2"))
     assert out.returncode == 0, out.stderr[-3000:]
@@ -364,6 +364,50 @@ def test_bench_contract_torchrun(world):
         p = x[f"zero3_{sched}"]
         assert p["probe_busbw_gbps"] == c["all_gather"]["busbw_gbps"]
         assert p["implied_link_ms_per_step"] > 0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run (no --full; CPU, tiny model) times exactly --steps steps, prints the
+    one result line with the driver's fields and none of the sections that --full adds, and
+    --dump-outputs writes the last step's outputs as float32 / float64 .npy files that a second
+    run with the same arguments reproduces (same seeded inputs; CPU sums are ordered)."""
+    import json
+
+    import numpy as np
+
+    def run(d):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                              "--steps", "3", "--warmup", "1", "--model", "tiny-llama",
+                              "--seq_len", "32", "--micro_batch", "2", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=300,
+                             env=dict(os.environ, OMP_NUM_THREADS="2"))
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[-2000:]
+        return json.loads(lines[0])
+
+    j = run(tmp_path / "a")
+    run(tmp_path / "b")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, k
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0
+    assert abs(j["value"] - 2 * 32 / (j["ms_per_step"] / 1000)) / j["value"] < 0.02
+    x = j["extra"]
+    assert x["serve"] is None and x["comm"] is None and x["box"] is None
+    assert "zero3_release" not in x and "zero3_hybrid" not in x and "serve_tp" not in x
+    assert x["budget"]["ran"] == [] and x["budget"]["skipped"] == []
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["adapter_norms.npy", "adapter_sample.npy", "loss.npy"]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 * 2**20
+    assert np.load(tmp_path / "a" / "loss.npy")[0] == pytest.approx(x["final_loss"], abs=1e-4)
+    assert np.load(tmp_path / "a" / "adapter_sample.npy").size == j["config"]["trainable_params"]
+    assert (np.load(tmp_path / "a" / "adapter_norms.npy") > 0).all()
 
 
 def test_gemm_wave_split_plan():
@@ -413,7 +457,7 @@ def test_bench_tp_serving_section_and_deadline(deadline):
                           "--steps", "1", "--warmup", "1", "--model", "tiny-llama-gqa",
                           "--seq_len", "32", "--micro_batch", "2", "--partitioned", "",
                           "--serve_tp", "2", "--serve_tp_shape", "8,24,6",
-                          "--serve_tp_deadline", str(deadline)],
+                          "--serve_tp_deadline", str(deadline), "--full"],
                          capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, OMP_NUM_THREADS="2"))
     assert out.returncode == 0, out.stderr[-3000:]
@@ -520,7 +564,7 @@ def test_bench_wall_budget_skips_sections_torchrun():
                           "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
                           str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2",
                           "--steps", "1", "--warmup", "1", "--model", "tiny-llama", "--seq_len",
-                          "32", "--micro_batch", "2", "--wall_budget", "1"],
+                          "32", "--micro_batch", "2", "--wall_budget", "1", "--full"],
                          capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, OMP_NUM_THREADS="2"))
     assert out.returncode == 0, out.stderr[-3000:]
