@@ -38,6 +38,7 @@ def make_engine(a):
                        max_num_seqs=a.max_num_seqs, max_num_batched_tokens=a.max_batched_tokens,
                        prefill_boost=a.prefill_boost, use_graphs=not a.no_graphs, init="random",
                        async_scheduling=not a.sync_scheduling, kv_cache_dtype=a.kv_cache_dtype,
+                       quantization=getattr(a, "quantization", None),
                        tp_size=getattr(a, "tp", 1),
                        scheduling_policy=getattr(a, "scheduling_policy", "chunked"),
                        num_blocks=getattr(a, "num_blocks", None),
@@ -46,6 +47,15 @@ def make_engine(a):
     t0 = time.time()
     eng = LLMEngine(cfg)
     eng._bench_setup_s = time.time() - t0
+    import torch
+
+    if torch.cuda.is_available():
+        # what the weights leave for the KV cache: before / after the cache was allocated
+        free = torch.cuda.mem_get_info()[0]
+        kv = sum(t.numel() * t.element_size() for t in list(eng.runner.k_cache)
+                 + list(eng.runner.v_cache))
+        eng._bench_hbm = {"free_after_setup_gib": round(free / 2 ** 30, 2),
+                          "kv_cache_gib": round(kv / 2 ** 30, 2)}
     return eng
 
 
@@ -126,6 +136,8 @@ def bench_engine(a, eng=None) -> dict:
             "kv_blocks": eng.blocks.num_blocks, "preemptions": eng.scheduler.num_preemptions,
             "max_batched_tokens": a.max_batched_tokens, "steps": eng.stats["steps"],
             "async_scheduling": eng.async_sched, "kv_cache_dtype": a.kv_cache_dtype,
+            "quantization": getattr(a, "quantization", None),
+            "hbm": getattr(eng, "_bench_hbm", None),
             "setup_s": round(getattr(eng, "_bench_setup_s", 0.0), 1),
             "graphs": sorted(eng.runner._graphs),
             "shared_prefix": len(shared), "prefix_caching": eng.blocks.prefix_caching,
@@ -273,6 +285,8 @@ def main():
                     help="x token budget while at most max-num-seqs/4 sequences decode (1: off)")
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8"])
+    ap.add_argument("--quantization", default=None, choices=["fp8"],
+                    help="fp8 weight-only quantization of the decoder projections")
     ap.add_argument("--sync-scheduling", action="store_true",
                     help="engine mode: host waits for each step's tokens before the next step")
     ap.add_argument("--tp", type=int, default=1,

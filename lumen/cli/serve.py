@@ -56,6 +56,9 @@ def build_parser():
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8"],
                     help="KV-cache element type (fp8 = e4m3: 2x capacity, half the decode K/V reads)")
+    ap.add_argument("--quantization", default=None, choices=["fp8"],
+                    help="weight-only quantization (vLLM's flag): fp8 = decoder projections "
+                         "stored as e4m3 with per-output-row scales, 16-bit activations")
     ap.add_argument("--enable-prefix-caching", action="store_true",
                     help="share the cached K/V of equal leading prompt blocks across requests "
                          "(vLLM's flag; finished requests' blocks stay cached until evicted)")
@@ -111,7 +114,7 @@ def main(argv=None):
                        max_num_seqs=a.max_num_seqs, max_num_batched_tokens=budget,
                        prefill_boost=a.prefill_boost, tp_size=a.tp, seed=a.seed, use_graphs=not a.no_graphs,
                        scheduling_policy=policy,
-                       kv_cache_dtype=a.kv_cache_dtype,
+                       kv_cache_dtype=a.kv_cache_dtype, quantization=a.quantization,
                        enable_prefix_caching=a.enable_prefix_caching,
                        num_speculative_tokens=spec_k,
                        ngram_max=a.ngram_prompt_lookup_max, ngram_min=a.ngram_prompt_lookup_min,

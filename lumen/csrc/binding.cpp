@@ -72,6 +72,12 @@ hipError_t lumen_skinny_gemm(int, const void*, const void*, void*, int, int, int
                              long long, hipStream_t);
 hipError_t lumen_decode_gemm(int, const void*, const void*, void*, float*, int*, int, int, int,
                              long long, long long, int, int, int, int, int, hipStream_t);
+hipError_t lumen_w8_gemv(int, const void*, const void*, const float*, void*, int, int, int,
+                         long long, long long, hipStream_t);
+hipError_t lumen_w8_decode_gemm(int, const void*, const void*, const float*, void*, float*, int*,
+                                int, int, int, long long, long long, int, int, int, hipStream_t);
+hipError_t lumen_w8_dequant(int, const void*, const float*, void*, long long, long long,
+                            hipStream_t);
 hipError_t lumen_mlp_gemm(int, int, const void*, long long, const void*, long long, void*, long long,
                           void*, long long, const void*, long long, int, int, int, int, int, float*,
                           int*, int, hipStream_t);
@@ -280,6 +286,90 @@ void decode_gemm(const at::Tensor& x, const at::Tensor& w, at::Tensor& y,
                           static_cast<int>(bn), static_cast<int>(nw), static_cast<int>(s),
                           static_cast<int>(flags), cur_stream()),
         "decode_gemm");
+}
+
+// fp8 weight-only projections (kernels/w8_gemm.hip): q [N, K] e4m3fn, scale [N] f32, x / y 16-bit
+void need_w8(const at::Tensor& q, const at::Tensor& scale, const char* what) {
+  if (!q.is_cuda() || !scale.is_cuda() || q.dim() != 2 || !q.is_contiguous() ||
+      q.scalar_type() != at::kFloat8_e4m3fn || scale.scalar_type() != at::kFloat ||
+      scale.dim() != 1 || !scale.is_contiguous() || scale.size(0) != q.size(0))
+    throw std::invalid_argument(std::string("lumen: ") + what +
+                                " needs a contiguous e4m3fn [N, K] weight and f32 [N] scales on the GPU");
+}
+
+void need_w8_xy(const at::Tensor& x, const at::Tensor& q, const at::Tensor& y, const char* what) {
+  if (!x.is_cuda() || !y.is_cuda() || x.dim() != 2 || y.dim() != 2 || x.stride(1) != 1 ||
+      y.stride(1) != 1 || x.size(1) != q.size(1) || y.size(0) != x.size(0) ||
+      y.size(1) != q.size(0) || x.scalar_type() != y.scalar_type() ||
+      (x.scalar_type() != at::kBFloat16 && x.scalar_type() != at::kHalf) ||
+      x.device() != q.device() || y.device() != q.device())
+    throw std::invalid_argument(std::string("lumen: ") + what + " shape/layout/device mismatch");
+}
+
+// y [M, N] = x [M, K] @ (q * scale[:, None])^T, 1 <= M <= 4
+void w8_gemv(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale, at::Tensor& y) {
+  need_w8(q, scale, "w8_gemv");
+  need_w8_xy(x, q, y, "w8_gemv");
+  if (x.size(0) < 1 || x.size(0) > 4 || q.size(0) % 4 != 0 || q.size(1) % 16 != 0 ||
+      x.stride(0) % 8 != 0)
+    throw std::invalid_argument("lumen: w8_gemv needs 1 <= M <= 4, N % 4 == 0, K % 16 == 0 and "
+                                "an x row stride that is a multiple of 8");
+  check(lumen_w8_gemv(dcode(x), x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(), y.data_ptr(),
+                      static_cast<int>(x.size(0)), static_cast<int>(q.size(0)),
+                      static_cast<int>(q.size(1)), x.stride(0), y.stride(0), cur_stream()),
+        "w8_gemv");
+}
+
+// the same product on the MFMA kernel with block tile (bm, bn) and split-K s (s > 1: ws f32
+// slabs + cnt zeroed tile counters), M <= bm
+void w8_decode_gemm(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale,
+                    at::Tensor& y, const std::optional<at::Tensor>& ws,
+                    const std::optional<at::Tensor>& cnt, int64_t bm, int64_t bn, int64_t s) {
+  need_w8(q, scale, "w8_decode_gemm");
+  need_w8_xy(x, q, y, "w8_decode_gemm");
+  const bool variant = (bm == 64 && (bn == 64 || bn == 128)) ||
+                       (bm == 128 && (bn == 64 || bn == 128)) || (bm == 256 && bn == 64);
+  if (!variant)
+    throw std::invalid_argument("lumen: w8_decode_gemm (bm, bn) must be one of (64, 64), "
+                                "(64, 128), (128, 64), (128, 128), (256, 64)");
+  if (x.size(0) < 1 || x.size(0) > bm)
+    throw std::invalid_argument("lumen: w8_decode_gemm needs 1 <= M <= bm");
+  if (q.size(1) % 64 != 0 || q.size(0) % 4 != 0 || x.stride(0) % 8 != 0 ||
+      x.stride(0) < q.size(1) || y.stride(0) % 4 != 0)
+    throw std::invalid_argument("lumen: w8_decode_gemm needs K % 64 == 0, N % 4 == 0, an x row "
+                                "stride >= K that is a multiple of 8 and a y row stride that is "
+                                "a multiple of 4");
+  if (s < 1 || s > q.size(1) / 64)
+    throw std::invalid_argument("lumen: w8_decode_gemm needs 1 <= s <= K / 64");
+  const long long tiles = (q.size(0) + bn - 1) / bn;
+  if (s > 1) {
+    if (!ws || !cnt || !ws->is_cuda() || !cnt->is_cuda() || ws->device() != x.device() ||
+        cnt->device() != x.device() || !ws->is_contiguous() || !cnt->is_contiguous() ||
+        ws->scalar_type() != at::kFloat || cnt->scalar_type() != at::kInt)
+      throw std::invalid_argument("lumen: w8_decode_gemm split-K needs a contiguous f32 "
+                                  "workspace and int32 counters on x's device");
+    if (ws->numel() < tiles * s * bm * bn || cnt->numel() < tiles)
+      throw std::invalid_argument("lumen: w8_decode_gemm split-K workspace too small");
+  }
+  check(lumen_w8_decode_gemm(dcode(x), x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(),
+                             y.data_ptr(), s > 1 ? ws->data_ptr<float>() : nullptr,
+                             s > 1 ? cnt->data_ptr<int>() : nullptr, static_cast<int>(x.size(0)),
+                             static_cast<int>(q.size(0)), static_cast<int>(q.size(1)),
+                             x.stride(0), y.stride(0), static_cast<int>(bm), static_cast<int>(bn),
+                             static_cast<int>(s), cur_stream()),
+        "w8_decode_gemm");
+}
+
+// out [N, K] (16-bit) = q * scale[:, None], bit-identical to ops.quant.QuantWeight.dequant()
+void w8_dequant(const at::Tensor& q, const at::Tensor& scale, at::Tensor& out) {
+  need_w8(q, scale, "w8_dequant");
+  if (!out.is_cuda() || !out.is_contiguous() || out.dim() != 2 || out.size(0) != q.size(0) ||
+      out.size(1) != q.size(1) ||
+      (out.scalar_type() != at::kBFloat16 && out.scalar_type() != at::kHalf))
+    throw std::invalid_argument("lumen: w8_dequant needs a contiguous 16-bit [N, K] output");
+  check(lumen_w8_dequant(dcode(out), q.data_ptr(), scale.data_ptr<float>(), out.data_ptr(),
+                         q.size(0), q.size(1), cur_stream()),
+        "w8_dequant");
 }
 
 // training-shape MLP GEMMs with the SwiGLU in the epilogue (kernels/mlp_gemm.hip):
@@ -1065,6 +1155,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("skinny_gemm", &skinny_gemm);
   m.def("skinny_swiglu_gemm", &skinny_swiglu_gemm);
   m.def("decode_gemm", &decode_gemm);
+  m.def("w8_gemv", &w8_gemv);
+  m.def("w8_decode_gemm", &w8_decode_gemm);
+  m.def("w8_dequant", &w8_dequant);
   m.def("mlp_gemm", &mlp_gemm, py::arg("epi"), py::arg("x"), py::arg("w"), py::arg("c"),
         py::arg("act") = py::none(), py::arg("gu") = py::none(), py::arg("group_m") = 4,
         py::arg("ws") = py::none(), py::arg("cnt") = py::none(), py::arg("split") = 0);

@@ -12,6 +12,7 @@ from typing import Optional
 import torch
 
 from ._native import native, use_native
+from .quant import QuantWeight
 
 # Measured per shape against hipBLASLt with the tuned table (lumen/bench/skinny_bench.py
 # --m1-forms, profiles/r02_serve/m1_forms.jsonl): the rows-per-lane weight-streaming kernel
@@ -62,26 +63,33 @@ def decode_gemm(x: torch.Tensor, w: torch.Tensor, bm: int, bn: int, s: int, nw: 
     x in the k-tiled layout [K / 64, bm, 64] (``x_ktiled``) with ``m`` valid rows."""
     rows = x.shape[0] if not flags & 2 else int(m)
     y = out if out is not None else torch.empty(rows, w.shape[0], device=x.device, dtype=x.dtype)
-    ws = cnt = None
-    if s > 1:
-        # one slab workspace + ticket counters per (device, stream): split-K slabs and tickets
-        # of GEMMs on different streams never interleave (a side-stream GEMM gets its own)
-        key = _dg_key(x.device)
-        got = _dg_ws.get(key)
-        need = -(-w.shape[0] // bn) * s * bm * bn
-        if got is None or got[0].numel() < need or got[1].numel() < -(-w.shape[0] // bn):
-            # generous size; a superseded pair stays alive (_dg_old): a captured decode graph
-            # keeps pointing at the buffers it was captured with
-            n = max(need, 1 << 24)
-            if got is not None:
-                _dg_old.append(got)
-            got = (torch.empty(n, dtype=torch.float32, device=x.device),
-                   torch.zeros(max(4096, -(-w.shape[0] // bn)), dtype=torch.int32,
-                               device=x.device))
-            _dg_ws[key] = got
-        ws, cnt = got
+    ws, cnt = _dg_splitk_ws(x.device, w.shape[0], bm, bn, s)
     native().decode_gemm(x, w, y, ws, cnt, bm, bn, s, nw, flags)
     return y
+
+
+def _dg_splitk_ws(device, N: int, bm: int, bn: int, s: int) -> tuple:
+    """(slab workspace, ticket counters) for a split-K launch of ``s`` slices over [bm, bn]
+    tiles of N columns on the current stream; (None, None) for s == 1.  Shared by the 16-bit and
+    the fp8-weight decode GEMM: launches on one stream run one after the other, and every launch
+    leaves the counters zero."""
+    if s <= 1:
+        return None, None
+    # one slab workspace + ticket counters per (device, stream): split-K slabs and tickets
+    # of GEMMs on different streams never interleave (a side-stream GEMM gets its own)
+    key = _dg_key(device)
+    got = _dg_ws.get(key)
+    need = -(-N // bn) * s * bm * bn
+    if got is None or got[0].numel() < need or got[1].numel() < -(-N // bn):
+        # generous size; a superseded pair stays alive (_dg_old): a captured decode graph
+        # keeps pointing at the buffers it was captured with
+        n = max(need, 1 << 24)
+        if got is not None:
+            _dg_old.append(got)
+        got = (torch.empty(n, dtype=torch.float32, device=device),
+               torch.zeros(max(4096, -(-N // bn)), dtype=torch.int32, device=device))
+        _dg_ws[key] = got
+    return got
 
 
 def x_ktiled(x: torch.Tensor, bm: int = 256) -> torch.Tensor:
@@ -209,8 +217,125 @@ def mm_nt(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return y
 
 
-def linear_nt(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    """x [M, K] @ w[N, K]^T -> [M, N]."""
+# ---- fp8 weight-only projections (ops/quant.py QuantWeight, kernels/w8_gemm.hip) ---------------
+# M <= 4: the fp8 rows-per-lane GEMV at every N (the weight stream is the cost at every N);
+# 5 <= M <= 256: the W8A16 MFMA kernel where the measured plan table
+# (configs/kernels/w8_gemm_plans.json, derived from profiles/w8_serve) lists the shape; everything
+# else -- prefill / mixed steps, shapes the kernels refuse -- dequantises into a persistent 16-bit
+# scratch (w8_dequant) and takes the 16-bit path above unchanged (same GEMM shapes and leading
+# dimensions, so the TunableOp table still applies).  LUMEN_W8=0 forces that fallback everywhere.
+W8 = os.environ.get("LUMEN_W8", "1") != "0"
+W8_BMS = (64, 128, 256)
+W8_BNS = {64: (64, 128), 128: (64, 128), 256: (64,)}   # compiled (BM, BN) variants
+_w8_plans: Optional[dict] = None
+_w8_scratch: dict = {}
+_w8_old: list = []
+_w8_reserved: dict = {}
+
+
+def load_w8_plans(path: str) -> dict:
+    """{(N, K, BM): (BN, S)} from a plan file in decode_gemm_plans.json's format."""
+    import json
+
+    plans = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            for e in json.load(f).get("plans", []):
+                plans[(e["N"], e["K"], e["BM"])] = (e["BN"], e["S"])
+    return plans
+
+
+def w8_plans() -> dict:
+    """The shipped plan table (measured wins over the dequant + library fallback only)."""
+    global _w8_plans
+    if _w8_plans is None:
+        _w8_plans = load_w8_plans(os.environ.get("LUMEN_W8_PLANS", os.path.join(
+            os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
+            "configs", "kernels", "w8_gemm_plans.json")))
+    return _w8_plans
+
+
+def _w8_common_ok(x: torch.Tensor, w) -> bool:
+    return (x.dim() == 2 and x.dtype == w.dtype and x.dtype in (torch.bfloat16, torch.float16)
+            and x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.stride(0) >= w.shape[1]
+            and x.shape[1] == w.shape[1] and w.q.is_contiguous() and w.shape[0] % 4 == 0 and x.data_ptr() % 16 == 0)
+
+
+def w8_gemv_ok(x: torch.Tensor, w) -> bool:
+    return 0 < x.shape[0] <= 4 and _w8_common_ok(x, w) and w.shape[1] % 16 == 0
+
+
+def w8_plan(x: torch.Tensor, w) -> Optional[tuple]:
+    """(BM, BN, S) of the MFMA kernel for this call, None where it does not apply."""
+    if not (4 < x.shape[0] <= 256 and _w8_common_ok(x, w) and w.shape[1] % 64 == 0
+            and w.scale.data_ptr() % 16 == 0):
+        return None
+    bm = next(b for b in W8_BMS if x.shape[0] <= b)
+    p = w8_plans().get((w.shape[0], w.shape[1], bm))
+    return (bm,) + tuple(p) if p is not None else None
+
+
+def w8_decode_gemm(x: torch.Tensor, w, bm: int, bn: int, s: int,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = x @ (w.q * w.scale[:, None])^T on the W8A16 MFMA kernel with block tile (bm, bn) and
+    split-K s."""
+    y = out if out is not None else torch.empty(x.shape[0], w.shape[0], device=x.device,
+                                                dtype=x.dtype)
+    ws, cnt = _dg_splitk_ws(x.device, w.shape[0], bm, bn, s)
+    native().w8_decode_gemm(x, w.q, w.scale, y, ws, cnt, bm, bn, s)
+    return y
+
+
+def w8_reserve(device, numel: int) -> None:
+    """Size every later dequant scratch on ``device`` for at least ``numel`` elements (the
+    largest projection being served), so a scratch never grows after a decode graph captured
+    it."""
+    _w8_reserved[str(device)] = max(_w8_reserved.get(str(device), 0), int(numel))
+
+
+def w8_dequant(w, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The 16-bit weight of ``w`` (bit-identical to ``w.dequant()``), by default in the
+    persistent scratch of the current (device, stream): valid until the next call there."""
+    N, K = w.shape
+    if K % 16:
+        raise ValueError(f"fp8 weights on the GPU need K % 16 == 0, got K = {K}")
+    if out is None:
+        key = _dg_key(w.device) + (w.dtype,)
+        buf = _w8_scratch.get(key)
+        if buf is None or buf.numel() < N * K:
+            # a superseded scratch stays alive (_w8_old): a captured graph keeps pointing at it
+            if buf is not None:
+                _w8_old.append(buf)
+            buf = torch.empty(max(N * K, _w8_reserved.get(str(w.device), 0)), dtype=w.dtype,
+                              device=w.device)
+            _w8_scratch[key] = buf
+        out = buf[:N * K].view(N, K)
+    native().w8_dequant(w.q, w.scale, out)
+    return out
+
+
+def _linear_w8(x: torch.Tensor, w) -> torch.Tensor:
+    if not use_native(x):
+        return x @ w.dequant().to(x.dtype).t()
+    if x.dtype != w.dtype:
+        raise ValueError(f"fp8 weight of a {w.dtype} model applied to {x.dtype} activations")
+    # the GEMV at every M <= 4: the fastest of the fp8 routes there.  Known loss against 16-bit
+    # weights: at M = 3..4 on the wide projections it is slower than the 16-bit GEMV (M = 4:
+    # qkv 29.5 vs 25.5 us, gate|up 48.0 vs 38.7 us, profiles/w8_serve)
+    if W8 and w8_gemv_ok(x, w):
+        y = torch.empty(x.shape[0], w.shape[0], device=x.device, dtype=x.dtype)
+        native().w8_gemv(x, w.q, w.scale, y)
+        return y
+    p = w8_plan(x, w) if W8 else None
+    if p is not None:
+        return w8_decode_gemm(x, w, *p)
+    return linear_nt(x, w8_dequant(w))
+
+
+def linear_nt(x: torch.Tensor, w) -> torch.Tensor:
+    """x [M, K] @ w[N, K]^T -> [M, N]; ``w`` a 16-bit tensor or an fp8 ``QuantWeight``."""
+    if isinstance(w, QuantWeight):
+        return _linear_w8(x, w)
     if skinny_ok(x, w):
         y = torch.empty(x.shape[0], w.shape[0], device=x.device, dtype=x.dtype)
         native().skinny_gemm(x, w, y)
@@ -230,11 +355,13 @@ def linear_nt(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 SWIGLU_GEMV = os.environ.get("LUMEN_SWIGLU_GEMV", "0") == "1"
 
 
-def swiglu_linear_nt(gu: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+def swiglu_linear_nt(gu: torch.Tensor, w) -> torch.Tensor:
     """(silu(gu[:, :F]) * gu[:, F:]) @ w[N, F]^T, the MLP down projection."""
     from .activation import swiglu
 
     M, F = gu.shape[0], gu.shape[1] // 2
+    if isinstance(w, QuantWeight):
+        return linear_nt(swiglu(gu), w)
     if (SWIGLU_GEMV and 0 < M <= 4 and gu.dim() == 2 and gu.shape[1] == 2 * F
             and gu.stride(1) == 1 and gu.stride(0) % 8 == 0 and use_native(gu)
             and w.dim() == 2 and w.shape[1] == F and w.is_contiguous() and gu.dtype == w.dtype

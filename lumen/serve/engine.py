@@ -68,6 +68,10 @@ class EngineConfig:
     # automatic prefix caching (vLLM --enable-prefix-caching): prompts share the cached K/V of
     # equal leading full blocks; finished sequences' blocks stay cached until evicted
     enable_prefix_caching: bool = False
+    # weight-only quantization (vLLM --quantization): None = 16-bit weights; "fp8" = the decoder
+    # projections stored as e4m3fn with one f32 scale per output row (ops/quant.py), activations
+    # and accumulation unchanged; embedding, norms and LM head stay 16-bit
+    quantization: Optional[str] = None
     # speculative decoding by prompt lookup (vLLM --speculative-model "[ngram]"): up to this many
     # draft tokens per greedy sequence, copied from where the sequence's last n tokens (n from
     # ngram_max down to ngram_min) occurred before; a decode step then verifies every draft in
@@ -142,6 +146,9 @@ class LLMEngine:
 
             load_tuned_gemms()  # tuned hipBLASLt algorithms for the prefill/decode GEMM shapes
         dt = _DT[cfg.dtype] if dev.type == "cuda" else torch.float32
+        if cfg.quantization not in (None, "fp8"):
+            raise ValueError(f"quantization must be None or 'fp8', got {cfg.quantization}")
+        own_model = model is None   # a model passed in by the caller is left untouched
         if model is None:
             model = build_model(cfg.model, dtype=dt, device=dev, init=cfg.init, seed=cfg.seed)
         if cfg.adapter:
@@ -158,7 +165,11 @@ class LLMEngine:
             from ..parallel.dist import host_group
 
             host_group()
-        self.weights = ServeWeights(model, self.rank, self.tp)
+        # quantized after the adapter merge above; un-merged lora_modules stay 16-bit on top
+        self.weights = ServeWeights(model, self.rank, self.tp, cfg.quantization,
+                                    release=own_model and cfg.quantization is not None)
+        if cfg.quantization is not None and dev.type == "cuda":
+            torch.cuda.empty_cache()  # the released 16-bit projections become KV blocks below
         if cfg.kv_cache_dtype not in ("auto", "fp8"):
             raise ValueError(f"kv_cache_dtype must be 'auto' or 'fp8', got {cfg.kv_cache_dtype}")
         self.kv_dtype = torch.float8_e4m3fn if cfg.kv_cache_dtype == "fp8" else dt

@@ -51,20 +51,30 @@ DECODE_SPLIT_MIN = int(os.environ.get("LUMEN_DECODE_SPLIT", "0"))
 class LayerW:
     ln1: torch.Tensor
     ln2: torch.Tensor
-    qkv: torch.Tensor
-    o: torch.Tensor
+    qkv: torch.Tensor       # the four projections: 16-bit tensors, or ops.quant.QuantWeight
+    o: torch.Tensor         # under quantization="fp8"
     gate_up: torch.Tensor
     down: torch.Tensor
 
 
 class ServeWeights:
-    """Inference weights extracted from a (LoRA-merged) LlamaForCausalLM, TP-sliced."""
+    """Inference weights extracted from a (LoRA-merged) LlamaForCausalLM, TP-sliced.
 
-    def __init__(self, model, tp_rank: int = 0, tp_size: int = 1):
+    ``quantization="fp8"``: the q|k|v, o, gate|up and down weights of every layer become
+    ``QuantWeight``s (e4m3fn + one f32 scale per output row, ops/quant.py), quantized AFTER the
+    TP slicing -- a row-parallel rank scales its own K slice, and the partial products meet in
+    the existing all-reduce.  Embedding, norms and the LM head stay 16-bit.  ``release=True``
+    (the engine built the model itself) frees each layer's 16-bit projection storage as it goes."""
+
+    def __init__(self, model, tp_rank: int = 0, tp_size: int = 1,
+                 quantization: Optional[str] = None, release: bool = False):
         cfg: ModelConfig = model.config
         if cfg.arch != "llama":
             raise NotImplementedError("serving supports the Llama family")
+        if quantization not in (None, "fp8"):
+            raise ValueError(f"quantization must be None or 'fp8', got {quantization}")
         self.cfg = cfg
+        self.quantization = quantization
         nh, nkv, D, H, Fd = (cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim,
                              cfg.hidden_size, cfg.intermediate_size)
         if nh % tp_size or nkv % tp_size or Fd % tp_size:
@@ -85,6 +95,28 @@ class ServeWeights:
                 gu = torch.cat([GU[r * lf:(r + 1) * lf], GU[Fd + r * lf:Fd + (r + 1) * lf]],
                                0).contiguous()
                 dn = L.mlp.down_proj.weight[:, r * lf:(r + 1) * lf].contiguous()
+                if quantization == "fp8":
+                    from ..ops.gemm import w8_reserve
+                    from ..ops.quant import quantize_fp8_rows
+
+                    if qkv.is_cuda:
+                        for name, t in (("q|k|v", qkv), ("o", o), ("gate|up", gu), ("down", dn)):
+                            # kernels/w8_gemm.hip (the dequant fallback included) moves the
+                            # weights in 16-byte chunks: refused here, not at the first step
+                            if t.shape[1] % 16:
+                                raise ValueError(
+                                    f"quantization='fp8' on the GPU needs projection weights "
+                                    f"[N, K] with K % 16 == 0; this rank's {name} weight is "
+                                    f"{tuple(t.shape)}")
+                    qkv, o, gu, dn = (quantize_fp8_rows(t) for t in (qkv, o, gu, dn))
+                    if qkv.q.is_cuda:
+                        # the dequant fallback's scratch is sized once, for the largest projection
+                        w8_reserve(qkv.q.device, max(t.q.numel() for t in (qkv, o, gu, dn)))
+                    if release:
+                        for lin in (L.self_attn.qkv_proj, L.self_attn.o_proj, L.mlp.gate_up_proj,
+                                    L.mlp.down_proj):
+                            lin.weight.data = torch.empty(0, dtype=lin.weight.dtype,
+                                                          device=lin.weight.device)
                 self.layers.append(LayerW(L.input_layernorm.weight, L.post_attention_layernorm.weight,
                                           qkv, o, gu, dn))
         self.embed = model.embed_tokens.weight
