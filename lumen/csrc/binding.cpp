@@ -78,6 +78,14 @@ hipError_t lumen_w8_decode_gemm(int, const void*, const void*, const float*, voi
                                 int, int, int, long long, long long, int, int, int, hipStream_t);
 hipError_t lumen_w8_dequant(int, const void*, const float*, void*, long long, long long,
                             hipStream_t);
+hipError_t lumen_act_quant_fp8(int, const void*, void*, float*, int, int, long long, hipStream_t);
+hipError_t lumen_w8a8_gemv(int, const void*, const float*, const void*, const float*, void*, int,
+                           int, int, long long, long long, hipStream_t);
+hipError_t lumen_w8a8_decode_gemm(int, const void*, const float*, const void*, const float*, void*,
+                                  float*, int*, int, int, int, long long, long long, int, int, int,
+                                  int, hipStream_t);
+hipError_t lumen_w8a8_gemm(int, const void*, const float*, const void*, const float*, void*, int,
+                           int, int, long long, long long, hipStream_t);
 hipError_t lumen_mlp_gemm(int, int, const void*, long long, const void*, long long, void*, long long,
                           void*, long long, const void*, long long, int, int, int, int, int, float*,
                           int*, int, hipStream_t);
@@ -370,6 +378,115 @@ void w8_dequant(const at::Tensor& q, const at::Tensor& scale, at::Tensor& out) {
   check(lumen_w8_dequant(dcode(out), q.data_ptr(), scale.data_ptr<float>(), out.data_ptr(),
                          q.size(0), q.size(1), cur_stream()),
         "w8_dequant");
+}
+
+// fp8 activations x fp8 weights (kernels/w8a8_gemm.hip): xq [M, K] e4m3fn + sx [M] f32 per-token
+// scales, q [N, K] e4m3fn + scale [N] f32, y 16-bit
+void act_quant_fp8(const at::Tensor& x, at::Tensor& xq, at::Tensor& sx) {
+  if (!x.is_cuda() || !xq.is_cuda() || !sx.is_cuda() || x.dim() != 2 || x.stride(1) != 1 ||
+      (x.scalar_type() != at::kBFloat16 && x.scalar_type() != at::kHalf) || xq.dim() != 2 ||
+      !xq.is_contiguous() || xq.scalar_type() != at::kFloat8_e4m3fn || xq.size(0) != x.size(0) ||
+      xq.size(1) != x.size(1) || sx.dim() != 1 || !sx.is_contiguous() ||
+      sx.scalar_type() != at::kFloat || sx.size(0) != x.size(0) || xq.device() != x.device() ||
+      sx.device() != x.device())
+    throw std::invalid_argument("lumen: act_quant_fp8 needs 16-bit x [M, K] with unit column "
+                                "stride, contiguous e4m3fn xq [M, K] and f32 sx [M] on one GPU");
+  if (x.size(0) < 1 || x.size(1) < 16 || x.size(1) % 16 != 0 || x.stride(0) % 8 != 0 ||
+      x.stride(0) < x.size(1))
+    throw std::invalid_argument("lumen: act_quant_fp8 needs M >= 1, K % 16 == 0 and an x row "
+                                "stride >= K that is a multiple of 8");
+  check(lumen_act_quant_fp8(dcode(x), x.data_ptr(), xq.data_ptr(), sx.data_ptr<float>(),
+                            static_cast<int>(x.size(0)), static_cast<int>(x.size(1)), x.stride(0),
+                            cur_stream()),
+        "act_quant_fp8");
+}
+
+void need_w8a8(const at::Tensor& xq, const at::Tensor& sx, const at::Tensor& q,
+               const at::Tensor& y, const char* what) {
+  if (!xq.is_cuda() || !sx.is_cuda() || !y.is_cuda() || xq.dim() != 2 || y.dim() != 2 ||
+      xq.scalar_type() != at::kFloat8_e4m3fn || xq.stride(1) != 1 || y.stride(1) != 1 ||
+      xq.size(1) != q.size(1) || y.size(0) != xq.size(0) || y.size(1) != q.size(0) ||
+      (y.scalar_type() != at::kBFloat16 && y.scalar_type() != at::kHalf) || sx.dim() != 1 ||
+      !sx.is_contiguous() || sx.scalar_type() != at::kFloat || sx.size(0) != xq.size(0) ||
+      xq.device() != q.device() || y.device() != q.device() || sx.device() != q.device())
+    throw std::invalid_argument(std::string("lumen: ") + what + " shape/layout/device mismatch");
+  if (xq.size(0) < 1 || q.size(0) % 4 != 0 || q.size(1) % 16 != 0 || xq.stride(0) % 16 != 0 ||
+      xq.stride(0) < q.size(1) || y.stride(0) < q.size(0))
+    throw std::invalid_argument(std::string("lumen: ") + what + " needs M >= 1, N % 4 == 0, "
+                                "K % 16 == 0 and an xq row stride >= K that is a multiple of 16");
+}
+
+// y [M, N] = (xq @ q^T) * sx[:, None] * scale[None, :], 1 <= M <= 4
+void w8a8_gemv(const at::Tensor& xq, const at::Tensor& sx, const at::Tensor& q,
+               const at::Tensor& scale, at::Tensor& y) {
+  need_w8(q, scale, "w8a8_gemv");
+  need_w8a8(xq, sx, q, y, "w8a8_gemv");
+  if (xq.size(0) > 4) throw std::invalid_argument("lumen: w8a8_gemv needs 1 <= M <= 4");
+  check(lumen_w8a8_gemv(dcode(y), xq.data_ptr(), sx.data_ptr<float>(), q.data_ptr(),
+                        scale.data_ptr<float>(), y.data_ptr(), static_cast<int>(xq.size(0)),
+                        static_cast<int>(q.size(0)), static_cast<int>(q.size(1)), xq.stride(0),
+                        y.stride(0), cur_stream()),
+        "w8a8_gemv");
+}
+
+// the same product on the decode MFMA kernel with block tile (bm, bn), split-K s (s > 1: ws f32
+// slabs + cnt zeroed tile counters) and MFMA form (0: scaled K = 128, 1: non-scaled K = 32)
+void w8a8_decode_gemm(const at::Tensor& xq, const at::Tensor& sx, const at::Tensor& q,
+                      const at::Tensor& scale, at::Tensor& y, const std::optional<at::Tensor>& ws,
+                      const std::optional<at::Tensor>& cnt, int64_t bm, int64_t bn, int64_t s,
+                      int64_t form) {
+  need_w8(q, scale, "w8a8_decode_gemm");
+  need_w8a8(xq, sx, q, y, "w8a8_decode_gemm");
+  const bool variant = (bm == 64 && (bn == 64 || bn == 128)) ||
+                       (bm == 128 && (bn == 64 || bn == 128 || bn == 256)) ||
+                       (bm == 256 && (bn == 64 || bn == 128));
+  if (!variant)
+    throw std::invalid_argument("lumen: w8a8_decode_gemm (bm, bn) must be one of (64, 64), "
+                                "(64, 128), (128, 64), (128, 128), (128, 256), (256, 64), "
+                                "(256, 128)");
+  if (xq.size(0) > bm) throw std::invalid_argument("lumen: w8a8_decode_gemm needs 1 <= M <= bm");
+  if (y.stride(0) % 4 != 0)
+    throw std::invalid_argument("lumen: w8a8_decode_gemm needs a y row stride that is a multiple "
+                                "of 4");
+  if (s < 1 || s > (q.size(1) + 127) / 128)
+    throw std::invalid_argument("lumen: w8a8_decode_gemm needs 1 <= s <= ceil(K / 128)");
+  if (form != 0 && form != 1)
+    throw std::invalid_argument("lumen: w8a8_decode_gemm form must be 0 (scaled K = 128 MFMA) or "
+                                "1 (non-scaled K = 32 MFMA)");
+  const long long tiles = (q.size(0) + bn - 1) / bn;
+  if (s > 1) {
+    if (!ws || !cnt || !ws->is_cuda() || !cnt->is_cuda() || ws->device() != xq.device() ||
+        cnt->device() != xq.device() || !ws->is_contiguous() || !cnt->is_contiguous() ||
+        ws->scalar_type() != at::kFloat || cnt->scalar_type() != at::kInt)
+      throw std::invalid_argument("lumen: w8a8_decode_gemm split-K needs a contiguous f32 "
+                                  "workspace and int32 counters on xq's device");
+    if (ws->numel() < tiles * s * bm * bn || cnt->numel() < tiles)
+      throw std::invalid_argument("lumen: w8a8_decode_gemm split-K workspace too small");
+  }
+  check(lumen_w8a8_decode_gemm(dcode(y), xq.data_ptr(), sx.data_ptr<float>(), q.data_ptr(),
+                               scale.data_ptr<float>(), y.data_ptr(),
+                               s > 1 ? ws->data_ptr<float>() : nullptr,
+                               s > 1 ? cnt->data_ptr<int>() : nullptr,
+                               static_cast<int>(xq.size(0)), static_cast<int>(q.size(0)),
+                               static_cast<int>(q.size(1)), xq.stride(0), y.stride(0),
+                               static_cast<int>(bm), static_cast<int>(bn), static_cast<int>(s),
+                               static_cast<int>(form), cur_stream()),
+        "w8a8_decode_gemm");
+}
+
+// the same product on the 128 x 128 block-tiled kernel (prefill / mixed steps, M > 256)
+void w8a8_gemm(const at::Tensor& xq, const at::Tensor& sx, const at::Tensor& q,
+               const at::Tensor& scale, at::Tensor& y) {
+  need_w8(q, scale, "w8a8_gemm");
+  need_w8a8(xq, sx, q, y, "w8a8_gemm");
+  if (xq.size(0) <= 256) throw std::invalid_argument("lumen: w8a8_gemm needs M > 256");
+  if (y.stride(0) % 4 != 0)
+    throw std::invalid_argument("lumen: w8a8_gemm needs a y row stride that is a multiple of 4");
+  check(lumen_w8a8_gemm(dcode(y), xq.data_ptr(), sx.data_ptr<float>(), q.data_ptr(),
+                        scale.data_ptr<float>(), y.data_ptr(), static_cast<int>(xq.size(0)),
+                        static_cast<int>(q.size(0)), static_cast<int>(q.size(1)), xq.stride(0),
+                        y.stride(0), cur_stream()),
+        "w8a8_gemm");
 }
 
 // training-shape MLP GEMMs with the SwiGLU in the epilogue (kernels/mlp_gemm.hip):
@@ -1158,6 +1275,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("w8_gemv", &w8_gemv);
   m.def("w8_decode_gemm", &w8_decode_gemm);
   m.def("w8_dequant", &w8_dequant);
+  m.def("act_quant_fp8", &act_quant_fp8);
+  m.def("w8a8_gemv", &w8a8_gemv);
+  m.def("w8a8_decode_gemm", &w8a8_decode_gemm);
+  m.def("w8a8_gemm", &w8a8_gemm);
   m.def("mlp_gemm", &mlp_gemm, py::arg("epi"), py::arg("x"), py::arg("w"), py::arg("c"),
         py::arg("act") = py::none(), py::arg("gu") = py::none(), py::arg("group_m") = 4,
         py::arg("ws") = py::none(), py::arg("cnt") = py::none(), py::arg("split") = 0);

@@ -314,7 +314,141 @@ def w8_dequant(w, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     return out
 
 
+# ---- fp8 activations x fp8 weights (QuantWeight.act == "fp8", kernels/w8a8_gemm.hip) -----------
+# Every route computes ops/quant.py's one function: the activation-quant kernel once, then by M
+# the W8A8 GEMV (M <= 4), the decode MFMA kernel (5..256) or the block-tiled kernel (M > 256)
+# where the measured plan table (configs/kernels/w8a8_gemm_plans.json, derived from
+# profiles/w8a8_serve by lumen/bench/w8a8_bench.py) lists the bucket; everything else is the
+# fake-quant fallback: xq widened exactly to 16 bits, W dequantised into the weight-only path's
+# scratch, the 16-bit path, and the rows multiplied by sx.  LUMEN_W8=0 forces that fallback.
+W8A8_BMS = W8_BMS
+W8A8_BNS = {64: (64, 128), 128: (64, 128, 256), 256: (64, 128)}   # compiled (BM, BN) variants
+W8A8_FORMS = (0, 1)                     # 0: scaled K = 128 MFMA, 1: non-scaled K = 32 MFMA
+# measured (profiles/w8a8_serve): the decode kernel is bound by the weight stream and its x
+# staging, not by the matrix cores, and the two forms are within 1-3 % of each other at every
+# shape; summed over the best candidates of all 5 <= M <= 256 rows the non-scaled form is ahead
+# (1116 vs 1129 us), so it is the default and the plan table is derived for it
+W8A8_FORM = int(os.environ.get("LUMEN_W8A8_FORM", "1"))
+W8A8_GEMM_TILES = ((128, 128),)         # compiled block tiles of the large-M kernel
+W8A8_GEMM_BUCKETS = (512, 2048, 4096)   # M buckets of the large-M plans (the last: every M above)
+_w8a8_plans: Optional[dict] = None
+
+
+def load_w8a8_plans(path: str) -> dict:
+    """{(N, K, bucket): (BN, S)} from a plan file in w8_gemm_plans.json's format.  ``BM`` <= 256
+    is a decode-kernel bucket (and its block height); a larger ``BM`` is an M bucket of the
+    large-M kernel (``W8A8_GEMM_BUCKETS``), whose block tile is fixed."""
+    import json
+
+    plans = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            for e in json.load(f).get("plans", []):
+                plans[(e["N"], e["K"], e["BM"])] = (e["BN"], e["S"])
+    return plans
+
+
+def w8a8_plans() -> dict:
+    """The shipped plan table (measured wins over the fake-quant fallback only)."""
+    global _w8a8_plans
+    if _w8a8_plans is None:
+        _w8a8_plans = load_w8a8_plans(os.environ.get("LUMEN_W8A8_PLANS", os.path.join(
+            os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
+            "configs", "kernels", "w8a8_gemm_plans.json")))
+    return _w8a8_plans
+
+
+def w8a8_gemm_bucket(M: int) -> int:
+    return next((b for b in W8A8_GEMM_BUCKETS if M <= b), W8A8_GEMM_BUCKETS[-1])
+
+
+def w8a8_plan(M: int, w) -> Optional[tuple]:
+    """(BM, BN, S) of the decode kernel for 5 <= M <= 256, (bucket, BN, S) of the large-M kernel
+    for M > 256; None where the table does not list the bucket."""
+    if M <= 4 or w.shape[0] % 4 or w.scale.data_ptr() % 16:
+        return None
+    bm = next(b for b in W8A8_BMS if M <= b) if M <= 256 else w8a8_gemm_bucket(M)
+    p = w8a8_plans().get((w.shape[0], w.shape[1], bm))
+    return (bm,) + tuple(p) if p is not None else None
+
+
+def act_quant_fp8(x: torch.Tensor) -> tuple:
+    """(xq [M, K] e4m3fn, sx [M] f32) of 16-bit ``x`` on the GPU, bit-identical to
+    ``ops.quant.quantize_fp8_tokens``."""
+    M, K = x.shape
+    if K % 16:
+        raise ValueError(f"fp8 activations on the GPU need K % 16 == 0, got K = {K}")
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.stride(0) < K or x.data_ptr() % 16:
+        x = x.contiguous()
+    xq = torch.empty(M, K, device=x.device, dtype=torch.float8_e4m3fn)
+    sx = torch.empty(M, device=x.device, dtype=torch.float32)
+    native().act_quant_fp8(x, xq, sx)
+    return xq, sx
+
+
+def w8a8_gemv(xq: torch.Tensor, sx: torch.Tensor, w, out: Optional[torch.Tensor] = None):
+    y = out if out is not None else torch.empty(xq.shape[0], w.shape[0], device=xq.device,
+                                                dtype=w.dtype)
+    native().w8a8_gemv(xq, sx, w.q, w.scale, y)
+    return y
+
+
+def w8a8_decode_gemm(xq: torch.Tensor, sx: torch.Tensor, w, bm: int, bn: int, s: int,
+                     form: Optional[int] = None, out: Optional[torch.Tensor] = None):
+    """y = (xq @ w.q^T) * sx[:, None] * w.scale[None, :] on the W8A8 decode MFMA kernel with block
+    tile (bm, bn), split-K s and MFMA form (``W8A8_FORMS``)."""
+    y = out if out is not None else torch.empty(xq.shape[0], w.shape[0], device=xq.device,
+                                                dtype=w.dtype)
+    ws, cnt = _dg_splitk_ws(xq.device, w.shape[0], bm, bn, s)
+    native().w8a8_decode_gemm(xq, sx, w.q, w.scale, y, ws, cnt, bm, bn, s,
+                              W8A8_FORM if form is None else form)
+    return y
+
+
+def w8a8_gemm(xq: torch.Tensor, sx: torch.Tensor, w, out: Optional[torch.Tensor] = None):
+    """The same product on the block-tiled large-M kernel (M > 256)."""
+    y = out if out is not None else torch.empty(xq.shape[0], w.shape[0], device=xq.device,
+                                                dtype=w.dtype)
+    native().w8a8_gemm(xq, sx, w.q, w.scale, y)
+    return y
+
+
+def w8a8_fallback(xq: torch.Tensor, sx: torch.Tensor, w) -> torch.Tensor:
+    """Fake-quant: every e4m3 value is exact in bf16 / fp16, so the 16-bit path on (xq widened,
+    W dequantised) followed by the per-row sx computes the same function to within one extra
+    16-bit rounding of W * sw (and of the unscaled product)."""
+    y = linear_nt(xq.to(w.dtype), w8_dequant(w))
+    return (y.float() * sx[:, None]).to(w.dtype)
+
+
+def _linear_w8a8(x: torch.Tensor, w) -> torch.Tensor:
+    if not use_native(x):
+        from .quant import quantize_fp8_tokens
+
+        xq, sx = quantize_fp8_tokens(x)
+        return ((xq.float() @ w.q.float().t()) * sx[:, None] * w.scale[None, :]).to(x.dtype)
+    if x.dtype != w.dtype:
+        raise ValueError(f"fp8 weight of a {w.dtype} model applied to {x.dtype} activations")
+    if x.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"activations {tuple(x.shape)} do not match the weight {tuple(w.shape)}")
+    M = x.shape[0]
+    if M == 0:
+        return x.new_empty(0, w.shape[0])
+    xq, sx = act_quant_fp8(x)
+    if W8:
+        if M <= 4 and w.shape[0] % 4 == 0:
+            return w8a8_gemv(xq, sx, w)
+        p = w8a8_plan(M, w)
+        if p is not None:
+            return w8a8_decode_gemm(xq, sx, w, *p) if M <= 256 else w8a8_gemm(xq, sx, w)
+    return w8a8_fallback(xq, sx, w)
+
+
 def _linear_w8(x: torch.Tensor, w) -> torch.Tensor:
+    if w.act == "fp8":
+        return _linear_w8a8(x, w)
+    if w.act is not None:
+        raise ValueError(f"QuantWeight.act must be None or 'fp8', got {w.act}")
     if not use_native(x):
         return x @ w.dequant().to(x.dtype).t()
     if x.dtype != w.dtype:
@@ -333,7 +467,8 @@ def _linear_w8(x: torch.Tensor, w) -> torch.Tensor:
 
 
 def linear_nt(x: torch.Tensor, w) -> torch.Tensor:
-    """x [M, K] @ w[N, K]^T -> [M, N]; ``w`` a 16-bit tensor or an fp8 ``QuantWeight``."""
+    """x [M, K] @ w[N, K]^T -> [M, N]; ``w`` a 16-bit tensor or an fp8 ``QuantWeight`` (with
+    ``act="fp8"``: the product of the per-token quantized x, ops/quant.py)."""
     if isinstance(w, QuantWeight):
         return _linear_w8(x, w)
     if skinny_ok(x, w):

@@ -52,7 +52,7 @@ class LayerW:
     ln1: torch.Tensor
     ln2: torch.Tensor
     qkv: torch.Tensor       # the four projections: 16-bit tensors, or ops.quant.QuantWeight
-    o: torch.Tensor         # under quantization="fp8"
+    o: torch.Tensor         # under quantization="fp8" / "ptpc_fp8"
     gate_up: torch.Tensor
     down: torch.Tensor
 
@@ -63,16 +63,19 @@ class ServeWeights:
     ``quantization="fp8"``: the q|k|v, o, gate|up and down weights of every layer become
     ``QuantWeight``s (e4m3fn + one f32 scale per output row, ops/quant.py), quantized AFTER the
     TP slicing -- a row-parallel rank scales its own K slice, and the partial products meet in
-    the existing all-reduce.  Embedding, norms and the LM head stay 16-bit.  ``release=True``
-    (the engine built the model itself) frees each layer's 16-bit projection storage as it goes."""
+    the existing all-reduce.  ``quantization="ptpc_fp8"`` (W8A8): the same weights with
+    ``act="fp8"``, so every projection also quantizes its input per token row at run time (a
+    row-parallel rank its own K slice).  Embedding, norms and the LM head stay 16-bit.
+    ``release=True`` (the engine built the model itself) frees each layer's 16-bit projection
+    storage as it goes."""
 
     def __init__(self, model, tp_rank: int = 0, tp_size: int = 1,
                  quantization: Optional[str] = None, release: bool = False):
         cfg: ModelConfig = model.config
         if cfg.arch != "llama":
             raise NotImplementedError("serving supports the Llama family")
-        if quantization not in (None, "fp8"):
-            raise ValueError(f"quantization must be None or 'fp8', got {quantization}")
+        if quantization not in (None, "fp8", "ptpc_fp8"):
+            raise ValueError(f"quantization must be None, 'fp8' or 'ptpc_fp8', got {quantization}")
         self.cfg = cfg
         self.quantization = quantization
         nh, nkv, D, H, Fd = (cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim,
@@ -95,7 +98,7 @@ class ServeWeights:
                 gu = torch.cat([GU[r * lf:(r + 1) * lf], GU[Fd + r * lf:Fd + (r + 1) * lf]],
                                0).contiguous()
                 dn = L.mlp.down_proj.weight[:, r * lf:(r + 1) * lf].contiguous()
-                if quantization == "fp8":
+                if quantization is not None:
                     from ..ops.gemm import w8_reserve
                     from ..ops.quant import quantize_fp8_rows
 
@@ -105,10 +108,13 @@ class ServeWeights:
                             # weights in 16-byte chunks: refused here, not at the first step
                             if t.shape[1] % 16:
                                 raise ValueError(
-                                    f"quantization='fp8' on the GPU needs projection weights "
-                                    f"[N, K] with K % 16 == 0; this rank's {name} weight is "
+                                    f"quantization='{quantization}' on the GPU needs projection "
+                                    f"weights [N, K] with K % 16 == 0; this rank's {name} weight is "
                                     f"{tuple(t.shape)}")
                     qkv, o, gu, dn = (quantize_fp8_rows(t) for t in (qkv, o, gu, dn))
+                    if quantization == "ptpc_fp8":
+                        for t in (qkv, o, gu, dn):
+                            t.act = "fp8"
                     if qkv.q.is_cuda:
                         # the dequant fallback's scratch is sized once, for the largest projection
                         w8_reserve(qkv.q.device, max(t.q.numel() for t in (qkv, o, gu, dn)))
@@ -464,8 +470,20 @@ class ModelRunner:
         graph = torch.cuda.CUDAGraph()
         if self._graph_pool is None:
             self._graph_pool = torch.cuda.graph_pool_handle()
-        with torch.cuda.graph(graph, pool=self._graph_pool):
-            out = self._decode_eager(*args)
+        # no garbage collection inside the capture: a dead engine of this process that sits in a
+        # reference cycle is freed whenever the collector runs, and destroying ITS captured
+        # graphs while this stream is capturing is an error that aborts the process
+        # (torch.cuda.graph does not collect before capturing); it is freed after the capture
+        import gc
+
+        gc_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(graph, pool=self._graph_pool):
+                out = self._decode_eager(*args)
+        finally:
+            if gc_on:
+                gc.enable()
         self._graphs[bucket] = (graph, st, out)
         return self._graphs[bucket]
 
