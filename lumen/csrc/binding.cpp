@@ -86,6 +86,11 @@ hipError_t lumen_w8a8_decode_gemm(int, const void*, const float*, const void*, c
                                   int, hipStream_t);
 hipError_t lumen_w8a8_gemm(int, const void*, const float*, const void*, const float*, void*, int,
                            int, int, long long, long long, hipStream_t);
+hipError_t lumen_w4a8_decode_gemm(int, const void*, const float*, const void*, const void*, void*,
+                                  float*, int*, int, int, int, long long, long long, int, int, int,
+                                  hipStream_t);
+hipError_t lumen_w4_dequant(int, const void*, const void*, void*, long long, long long,
+                            hipStream_t);
 hipError_t lumen_mlp_gemm(int, int, const void*, long long, const void*, long long, void*, long long,
                           void*, long long, const void*, long long, int, int, int, int, int, float*,
                           int*, int, hipStream_t);
@@ -487,6 +492,81 @@ void w8a8_gemm(const at::Tensor& xq, const at::Tensor& sx, const at::Tensor& q,
                         static_cast<int>(q.size(0)), static_cast<int>(q.size(1)), xq.stride(0),
                         y.stride(0), cur_stream()),
         "w8a8_gemm");
+}
+
+// fp8 activations x MXFP4 weights (kernels/w4a8_gemm.hip): q [N, Kp / 2] uint8 e2m1 code pairs and
+// scale [N, Kp / 32] uint8 E8M0 block exponents, Kp = K rounded up to 32 (ops/quant.py Mxfp4Weight)
+void need_w4(const at::Tensor& q, const at::Tensor& scale, int64_t K, const char* what) {
+  if (!q.is_cuda() || !scale.is_cuda() || q.dim() != 2 || scale.dim() != 2 || !q.is_contiguous() ||
+      !scale.is_contiguous() || q.scalar_type() != at::kByte || scale.scalar_type() != at::kByte ||
+      q.device() != scale.device() || K < 1 || scale.size(0) != q.size(0) ||
+      scale.size(1) != (K + 31) / 32 || q.size(1) != 16 * scale.size(1))
+    throw std::invalid_argument(std::string("lumen: ") + what + " needs contiguous uint8 codes "
+                                "[N, 16 ceil(K / 32)] and block scales [N, ceil(K / 32)] on the GPU");
+}
+
+// y [M, N] = (xq @ wdq^T) * sx[:, None] on the decode MFMA kernel with block tile (bm, bn) and
+// split-K s (s > 1: ws f32 slabs + cnt zeroed tile counters), M <= bm
+void w4a8_decode_gemm(const at::Tensor& xq, const at::Tensor& sx, const at::Tensor& q,
+                      const at::Tensor& scale, at::Tensor& y, const std::optional<at::Tensor>& ws,
+                      const std::optional<at::Tensor>& cnt, int64_t bm, int64_t bn, int64_t s) {
+  const char* what = "w4a8_decode_gemm";
+  if (!xq.is_cuda() || xq.dim() != 2)
+    throw std::invalid_argument("lumen: w4a8_decode_gemm shape/layout/device mismatch");
+  const int64_t K = xq.size(1), N = q.dim() == 2 ? q.size(0) : 0;
+  need_w4(q, scale, K, what);
+  if (!sx.is_cuda() || !y.is_cuda() || y.dim() != 2 || xq.scalar_type() != at::kFloat8_e4m3fn ||
+      xq.stride(1) != 1 || y.stride(1) != 1 || y.size(0) != xq.size(0) || y.size(1) != N ||
+      (y.scalar_type() != at::kBFloat16 && y.scalar_type() != at::kHalf) || sx.dim() != 1 ||
+      !sx.is_contiguous() || sx.scalar_type() != at::kFloat || sx.size(0) != xq.size(0) ||
+      xq.device() != q.device() || y.device() != q.device() || sx.device() != q.device())
+    throw std::invalid_argument("lumen: w4a8_decode_gemm shape/layout/device mismatch");
+  if (xq.size(0) < 1 || N % 4 != 0 || K % 16 != 0 || xq.stride(0) % 16 != 0 ||
+      xq.stride(0) < K || y.stride(0) < N || y.stride(0) % 4 != 0)
+    throw std::invalid_argument("lumen: w4a8_decode_gemm needs M >= 1, N % 4 == 0, K % 16 == 0, an "
+                                "xq row stride >= K that is a multiple of 16 and a y row stride "
+                                "that is a multiple of 4");
+  const bool variant = ((bm == 16 || bm == 64 || bm == 128) && (bn == 64 || bn == 128)) ||
+                       (bm == 256 && bn == 64);
+  if (!variant)
+    throw std::invalid_argument("lumen: w4a8_decode_gemm (bm, bn) must be one of (16, 64), "
+                                "(16, 128), (64, 64), (64, 128), (128, 64), (128, 128), (256, 64)");
+  if (xq.size(0) > bm) throw std::invalid_argument("lumen: w4a8_decode_gemm needs 1 <= M <= bm");
+  if (s < 1 || s > (K + 127) / 128)
+    throw std::invalid_argument("lumen: w4a8_decode_gemm needs 1 <= s <= ceil(K / 128)");
+  const long long tiles = (N + bn - 1) / bn;
+  if (s > 1) {
+    if (!ws || !cnt || !ws->is_cuda() || !cnt->is_cuda() || ws->device() != xq.device() ||
+        cnt->device() != xq.device() || !ws->is_contiguous() || !cnt->is_contiguous() ||
+        ws->scalar_type() != at::kFloat || cnt->scalar_type() != at::kInt)
+      throw std::invalid_argument("lumen: w4a8_decode_gemm split-K needs a contiguous f32 "
+                                  "workspace and int32 counters on xq's device");
+    if (ws->numel() < tiles * s * bm * bn || cnt->numel() < tiles)
+      throw std::invalid_argument("lumen: w4a8_decode_gemm split-K workspace too small");
+  }
+  check(lumen_w4a8_decode_gemm(dcode(y), xq.data_ptr(), sx.data_ptr<float>(), q.data_ptr(),
+                               scale.data_ptr(), y.data_ptr(),
+                               s > 1 ? ws->data_ptr<float>() : nullptr,
+                               s > 1 ? cnt->data_ptr<int>() : nullptr,
+                               static_cast<int>(xq.size(0)), static_cast<int>(N),
+                               static_cast<int>(K), xq.stride(0), y.stride(0),
+                               static_cast<int>(bm), static_cast<int>(bn), static_cast<int>(s),
+                               cur_stream()),
+        what);
+}
+
+// out [N, K] (16-bit) = code * 2^(scale - 127), bit-identical to ops.quant.Mxfp4Weight.dequant()
+void w4_dequant(const at::Tensor& q, const at::Tensor& scale, at::Tensor& out) {
+  if (!out.is_cuda() || !out.is_contiguous() || out.dim() != 2 ||
+      (out.scalar_type() != at::kBFloat16 && out.scalar_type() != at::kHalf))
+    throw std::invalid_argument("lumen: w4_dequant needs a contiguous 16-bit [N, K] output");
+  need_w4(q, scale, out.size(1), "w4_dequant");
+  if (out.size(0) != q.size(0) || out.size(1) % 8 != 0 || out.device() != q.device())
+    throw std::invalid_argument("lumen: w4_dequant needs an [N, K] output on the weight's GPU "
+                                "with K % 8 == 0");
+  check(lumen_w4_dequant(dcode(out), q.data_ptr(), scale.data_ptr(), out.data_ptr(), q.size(0),
+                         out.size(1), cur_stream()),
+        "w4_dequant");
 }
 
 // training-shape MLP GEMMs with the SwiGLU in the epilogue (kernels/mlp_gemm.hip):
@@ -1279,6 +1359,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("w8a8_gemv", &w8a8_gemv);
   m.def("w8a8_decode_gemm", &w8a8_decode_gemm);
   m.def("w8a8_gemm", &w8a8_gemm);
+  m.def("w4a8_decode_gemm", &w4a8_decode_gemm);
+  m.def("w4_dequant", &w4_dequant);
   m.def("mlp_gemm", &mlp_gemm, py::arg("epi"), py::arg("x"), py::arg("w"), py::arg("c"),
         py::arg("act") = py::none(), py::arg("gu") = py::none(), py::arg("group_m") = 4,
         py::arg("ws") = py::none(), py::arg("cnt") = py::none(), py::arg("split") = 0);

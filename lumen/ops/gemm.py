@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 
 from ._native import native, use_native
-from .quant import QuantWeight
+from .quant import Mxfp4Weight, QuantWeight
 
 # Measured per shape against hipBLASLt with the tuned table (lumen/bench/skinny_bench.py
 # --m1-forms, profiles/r02_serve/m1_forms.jsonl): the rows-per-lane weight-streaming kernel
@@ -444,6 +444,112 @@ def _linear_w8a8(x: torch.Tensor, w) -> torch.Tensor:
     return w8a8_fallback(xq, sx, w)
 
 
+# ---- fp8 activations x MXFP4 weights (ops/quant.py Mxfp4Weight, kernels/w4a8_gemm.hip) ----------
+# One function on every route (ops/quant.py): the activation-quant kernel once, then by M: M <= 16
+# always the BM = 16 decode kernel ((BN, S) from the plan table where listed, else
+# ``w4a8_default_plan``); 17 <= M <= 256 the kernel where the measured plan table
+# (configs/kernels/w4a8_gemm_plans.json, written by lumen/bench/w4a8_bench.py) lists the bucket;
+# everything else the fallback: w4_dequant into the weight-only path's scratch, xq widened exactly
+# to 16 bits, the 16-bit path, the rows multiplied by sx.  LUMEN_W8=0 forces that fallback.
+W4A8_BMS = (16, 64, 128, 256)
+W4A8_BNS = {16: (64, 128), 64: (64, 128), 128: (64, 128), 256: (64,)}   # compiled variants
+_w4a8_plans: Optional[dict] = None
+
+
+def load_w4a8_plans(path: str) -> dict:
+    """{(N, K, BM): (BN, S)} from a plan file in w8_gemm_plans.json's format."""
+    return load_w8_plans(path)
+
+
+def w4a8_plans() -> dict:
+    """The shipped plan table (measured wins over the fallback only)."""
+    global _w4a8_plans
+    if _w4a8_plans is None:
+        _w4a8_plans = load_w4a8_plans(os.environ.get("LUMEN_W4A8_PLANS", os.path.join(
+            os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
+            "configs", "kernels", "w4a8_gemm_plans.json")))
+    return _w4a8_plans
+
+
+def w4a8_default_plan(N: int, K: int) -> tuple:
+    """(BN, S) of the BM = 16 kernel for a shape the table does not list: 64-column tiles and
+    enough split-K for two workgroups on each of the 256 CUs (N = 4096: 64 tiles x 8 slices),
+    every slice keeping at least four k128 steps."""
+    tiles, kt = -(-N // 64), -(-K // 128)
+    return 64, max(1, min(-(-512 // tiles), kt // 4, 16))
+
+
+def w4a8_plan(M: int, w) -> Optional[tuple]:
+    """(BM, BN, S) of the decode kernel for this call, None where the fallback runs."""
+    if M > 256 or w.shape[0] % 4:
+        return None
+    bm = next(b for b in W4A8_BMS if M <= b)
+    p = w4a8_plans().get((w.shape[0], w.shape[1], bm))
+    if p is None and bm == 16:
+        p = w4a8_default_plan(*w.shape)
+    return (bm,) + tuple(p) if p is not None else None
+
+
+def w4a8_decode_gemm(xq: torch.Tensor, sx: torch.Tensor, w, bm: int, bn: int, s: int,
+                     out: Optional[torch.Tensor] = None):
+    """y = (xq @ wdq^T) * sx[:, None] on the W4A8 decode MFMA kernel with block tile (bm, bn) and
+    split-K s."""
+    y = out if out is not None else torch.empty(xq.shape[0], w.shape[0], device=xq.device,
+                                                dtype=w.dtype)
+    ws, cnt = _dg_splitk_ws(xq.device, w.shape[0], bm, bn, s)
+    native().w4a8_decode_gemm(xq, sx, w.q, w.scale, y, ws, cnt, bm, bn, s)
+    return y
+
+
+def w4_dequant(w, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The 16-bit weight of ``w`` (bit-identical to ``w.dequant()``), by default in the fp8
+    modes' persistent scratch of the current (device, stream): valid until the next call there."""
+    N, K = w.shape
+    if K % 16:
+        raise ValueError(f"mxfp4 weights on the GPU need K % 16 == 0, got K = {K}")
+    if out is None:
+        key = _dg_key(w.device) + (w.dtype,)
+        buf = _w8_scratch.get(key)
+        if buf is None or buf.numel() < N * K:
+            # a superseded scratch stays alive (_w8_old): a captured graph keeps pointing at it
+            if buf is not None:
+                _w8_old.append(buf)
+            buf = torch.empty(max(N * K, _w8_reserved.get(str(w.device), 0)), dtype=w.dtype,
+                              device=w.device)
+            _w8_scratch[key] = buf
+        out = buf[:N * K].view(N, K)
+    native().w4_dequant(w.q, w.scale, out)
+    return out
+
+
+def w4a8_fallback(xq: torch.Tensor, sx: torch.Tensor, w) -> torch.Tensor:
+    """Every e4m3 value is exact in bf16 / fp16, so the 16-bit path on (xq widened, W
+    dequantised) followed by the per-row sx computes the same function to within one extra 16-bit
+    rounding of the unscaled product (and, in fp16, of a weight outside its range)."""
+    y = linear_nt(xq.to(w.dtype), w4_dequant(w))
+    return (y.float() * sx[:, None]).to(w.dtype)
+
+
+def _linear_w4a8(x: torch.Tensor, w) -> torch.Tensor:
+    if not use_native(x):
+        from .quant import quantize_fp8_tokens
+
+        xq, sx = quantize_fp8_tokens(x)
+        return ((xq.float() @ w.dequant_f32().t()) * sx[:, None]).to(x.dtype)
+    if x.dtype != w.dtype:
+        raise ValueError(f"mxfp4 weight of a {w.dtype} model applied to {x.dtype} activations")
+    if x.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"activations {tuple(x.shape)} do not match the weight {tuple(w.shape)}")
+    M = x.shape[0]
+    if M == 0:
+        return x.new_empty(0, w.shape[0])
+    xq, sx = act_quant_fp8(x)
+    p = w4a8_plan(M, w) if W8 else None
+    if p is not None:
+        return w4a8_decode_gemm(xq, sx, w, *p)
+    return w4a8_fallback(xq, sx, w)
+
+
 def _linear_w8(x: torch.Tensor, w) -> torch.Tensor:
     if w.act == "fp8":
         return _linear_w8a8(x, w)
@@ -467,10 +573,13 @@ def _linear_w8(x: torch.Tensor, w) -> torch.Tensor:
 
 
 def linear_nt(x: torch.Tensor, w) -> torch.Tensor:
-    """x [M, K] @ w[N, K]^T -> [M, N]; ``w`` a 16-bit tensor or an fp8 ``QuantWeight`` (with
-    ``act="fp8"``: the product of the per-token quantized x, ops/quant.py)."""
+    """x [M, K] @ w[N, K]^T -> [M, N]; ``w`` a 16-bit tensor, an fp8 ``QuantWeight`` (with
+    ``act="fp8"``: the product of the per-token quantized x, ops/quant.py) or an ``Mxfp4Weight``
+    (always with the per-token quantized x)."""
     if isinstance(w, QuantWeight):
         return _linear_w8(x, w)
+    if isinstance(w, Mxfp4Weight):
+        return _linear_w4a8(x, w)
     if skinny_ok(x, w):
         y = torch.empty(x.shape[0], w.shape[0], device=x.device, dtype=x.dtype)
         native().skinny_gemm(x, w, y)
@@ -495,7 +604,7 @@ def swiglu_linear_nt(gu: torch.Tensor, w) -> torch.Tensor:
     from .activation import swiglu
 
     M, F = gu.shape[0], gu.shape[1] // 2
-    if isinstance(w, QuantWeight):
+    if isinstance(w, (QuantWeight, Mxfp4Weight)):
         return linear_nt(swiglu(gu), w)
     if (SWIGLU_GEMV and 0 < M <= 4 and gu.dim() == 2 and gu.shape[1] == 2 * F
             and gu.stride(1) == 1 and gu.stride(0) % 8 == 0 and use_native(gu)

@@ -71,8 +71,9 @@ class EngineConfig:
     # weight-only quantization (vLLM --quantization): None = 16-bit weights; "fp8" = the decoder
     # projections stored as e4m3fn with one f32 scale per output row (ops/quant.py), activations
     # and accumulation unchanged; "ptpc_fp8" = the same weights with the projection inputs
-    # quantized to e4m3fn per token at run time (W8A8, vLLM's ptpc_fp8 on ROCm); embedding, norms
-    # and LM head stay 16-bit
+    # quantized to e4m3fn per token at run time (W8A8, vLLM's ptpc_fp8 on ROCm); "mxfp4" = MXFP4
+    # weights (e2m1 + one E8M0 scale per 32 k, round to nearest) with the same per-token e4m3fn
+    # inputs (W4A8); embedding, norms and LM head stay 16-bit
     quantization: Optional[str] = None
     # speculative decoding by prompt lookup (vLLM --speculative-model "[ngram]"): up to this many
     # draft tokens per greedy sequence, copied from where the sequence's last n tokens (n from
@@ -148,8 +149,8 @@ class LLMEngine:
 
             load_tuned_gemms()  # tuned hipBLASLt algorithms for the prefill/decode GEMM shapes
         dt = _DT[cfg.dtype] if dev.type == "cuda" else torch.float32
-        if cfg.quantization not in (None, "fp8", "ptpc_fp8"):
-            raise ValueError("quantization must be None, 'fp8' or 'ptpc_fp8', got "
+        if cfg.quantization not in (None, "fp8", "ptpc_fp8", "mxfp4"):
+            raise ValueError("quantization must be None, 'fp8', 'ptpc_fp8' or 'mxfp4', got "
                              f"{cfg.quantization}")
         own_model = model is None   # a model passed in by the caller is left untouched
         if model is None:

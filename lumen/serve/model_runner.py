@@ -52,7 +52,7 @@ class LayerW:
     ln1: torch.Tensor
     ln2: torch.Tensor
     qkv: torch.Tensor       # the four projections: 16-bit tensors, or ops.quant.QuantWeight
-    o: torch.Tensor         # under quantization="fp8" / "ptpc_fp8"
+    o: torch.Tensor         # under quantization="fp8" / "ptpc_fp8", Mxfp4Weight under "mxfp4"
     gate_up: torch.Tensor
     down: torch.Tensor
 
@@ -65,7 +65,10 @@ class ServeWeights:
     TP slicing -- a row-parallel rank scales its own K slice, and the partial products meet in
     the existing all-reduce.  ``quantization="ptpc_fp8"`` (W8A8): the same weights with
     ``act="fp8"``, so every projection also quantizes its input per token row at run time (a
-    row-parallel rank its own K slice).  Embedding, norms and the LM head stay 16-bit.
+    row-parallel rank its own K slice).  ``quantization="mxfp4"`` (W4A8): the four weights become
+    ``Mxfp4Weight``s (e2m1 codes + one E8M0 scale per 32 consecutive k, a row-parallel rank forming
+    the blocks over its own K slice) and the inputs are quantized as under ``ptpc_fp8``.
+    Embedding, norms and the LM head stay 16-bit.
     ``release=True`` (the engine built the model itself) frees each layer's 16-bit projection
     storage as it goes."""
 
@@ -74,8 +77,9 @@ class ServeWeights:
         cfg: ModelConfig = model.config
         if cfg.arch != "llama":
             raise NotImplementedError("serving supports the Llama family")
-        if quantization not in (None, "fp8", "ptpc_fp8"):
-            raise ValueError(f"quantization must be None, 'fp8' or 'ptpc_fp8', got {quantization}")
+        if quantization not in (None, "fp8", "ptpc_fp8", "mxfp4"):
+            raise ValueError("quantization must be None, 'fp8', 'ptpc_fp8' or 'mxfp4', got "
+                             f"{quantization}")
         self.cfg = cfg
         self.quantization = quantization
         nh, nkv, D, H, Fd = (cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim,
@@ -100,8 +104,9 @@ class ServeWeights:
                 dn = L.mlp.down_proj.weight[:, r * lf:(r + 1) * lf].contiguous()
                 if quantization is not None:
                     from ..ops.gemm import w8_reserve
-                    from ..ops.quant import quantize_fp8_rows
+                    from ..ops.quant import quantize_fp8_rows, quantize_mxfp4_rows
 
+                    quantize = quantize_mxfp4_rows if quantization == "mxfp4" else quantize_fp8_rows
                     if qkv.is_cuda:
                         for name, t in (("q|k|v", qkv), ("o", o), ("gate|up", gu), ("down", dn)):
                             # kernels/w8_gemm.hip (the dequant fallback included) moves the
@@ -111,13 +116,14 @@ class ServeWeights:
                                     f"quantization='{quantization}' on the GPU needs projection "
                                     f"weights [N, K] with K % 16 == 0; this rank's {name} weight is "
                                     f"{tuple(t.shape)}")
-                    qkv, o, gu, dn = (quantize_fp8_rows(t) for t in (qkv, o, gu, dn))
+                    qkv, o, gu, dn = (quantize(t) for t in (qkv, o, gu, dn))
                     if quantization == "ptpc_fp8":
                         for t in (qkv, o, gu, dn):
                             t.act = "fp8"
                     if qkv.q.is_cuda:
                         # the dequant fallback's scratch is sized once, for the largest projection
-                        w8_reserve(qkv.q.device, max(t.q.numel() for t in (qkv, o, gu, dn)))
+                        w8_reserve(qkv.q.device, max(t.shape[0] * t.shape[1]
+                                                     for t in (qkv, o, gu, dn)))
                     if release:
                         for lin in (L.self_attn.qkv_proj, L.self_attn.o_proj, L.mlp.gate_up_proj,
                                     L.mlp.down_proj):
