@@ -285,10 +285,12 @@ def main():
                     help="x token budget while at most max-num-seqs/4 sequences decode (1: off)")
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8"])
-    ap.add_argument("--quantization", default=None, choices=["fp8", "ptpc_fp8", "mxfp4"],
+    ap.add_argument("--quantization", default=None,
+                    choices=["fp8", "ptpc_fp8", "mxfp4", "mxfp4_a16"],
                     help="quantization of the decoder projections: fp8 = weight-only, "
                          "ptpc_fp8 = per-token fp8 activations too (W8A8), mxfp4 = MXFP4 weights "
-                         "with those activations (W4A8)")
+                         "with those activations (W4A8), mxfp4_a16 = MXFP4 weights, 16-bit "
+                         "activations")
     ap.add_argument("--sync-scheduling", action="store_true",
                     help="engine mode: host waits for each step's tokens before the next step")
     ap.add_argument("--tp", type=int, default=1,

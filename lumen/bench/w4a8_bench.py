@@ -27,18 +27,22 @@ MS = (1, 2, 4, 8, 16, 32, 64, 128, 192, 256)
 SPLITS = (1, 2, 4, 8, 16)
 
 
-def bucket_of(M):
-    from lumen.ops.gemm import W4A8_BMS
+def bucket_of(M, bms=None):
+    """The block height that serves M rows (``bms``: another kernel's block heights)."""
+    if bms is None:
+        from lumen.ops.gemm import W4A8_BMS as bms
 
-    return next(b for b in W4A8_BMS if M <= b)
+    return next(b for b in bms if M <= b)
 
 
-def candidates(M, N, K):
-    from lumen.ops.gemm import W4A8_BNS
+def candidates(M, N, K, bns=None):
+    """Every (BM, BN, S) to time at M rows (``bns``: another kernel's compiled variants)."""
+    if bns is None:
+        from lumen.ops.gemm import W4A8_BNS as bns
 
-    bm = bucket_of(M)
+    bm = bucket_of(M, sorted(bns))
     out = []
-    for bn in W4A8_BNS[bm]:
+    for bn in bns[bm]:
         tiles = -(-N // bn)
         for s in SPLITS:
             # at most ~4 blocks per CU, at least 4 k128 steps per slice
@@ -48,16 +52,16 @@ def candidates(M, N, K):
     return out
 
 
-def derive_plans(rows):
-    """One (BN, S) per (N, K, bucket): the candidate with the least total time over the bucket's
-    measured M, listed only if it beat the fallback at every one of them."""
+def derive_plans(rows, prefix="w4a8", bms=None):
+    """One (BN, S) per (N, K, bucket): the ``prefix``_bm*_bn*_s* candidate with the least total
+    time over the bucket's measured M, listed only if it beat the fallback at every one of them."""
     buckets = {}
     for r in rows:
         for name, us in r["us"].items():
-            if not name.startswith("w4a8_bm"):
+            if not name.startswith(prefix + "_bm"):
                 continue
-            _, bn, s = (int(t.lstrip("bmns")) for t in name[5:].split("_"))
-            buckets.setdefault((r["N"], r["K"], bucket_of(r["M"])), {}).setdefault(
+            _, bn, s = (int(t.lstrip("bmns")) for t in name[len(prefix) + 1:].split("_"))
+            buckets.setdefault((r["N"], r["K"], bucket_of(r["M"], bms)), {}).setdefault(
                 (bn, s), []).append((r["M"], us, r["us"]["fallback"]))
     plans = []
     for (N, K, b), cands in sorted(buckets.items()):

@@ -56,11 +56,12 @@ def build_parser():
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8"],
                     help="KV-cache element type (fp8 = e4m3: 2x capacity, half the decode K/V reads)")
-    ap.add_argument("--quantization", default=None, choices=["fp8", "ptpc_fp8", "mxfp4"],
+    ap.add_argument("--quantization", default=None, choices=["fp8", "ptpc_fp8", "mxfp4", "mxfp4_a16"],
                     help="quantization (vLLM's flag): fp8 = decoder projections stored as e4m3 "
                          "with per-output-row scales, 16-bit activations; ptpc_fp8 = the same "
                          "weights with per-token dynamic e4m3 activations (W8A8); mxfp4 = MXFP4 "
-                         "weights (round to nearest, no calibration) with those activations (W4A8)")
+                         "weights (round to nearest, no calibration) with those activations (W4A8); "
+                         "mxfp4_a16 = the same MXFP4 weights with 16-bit activations (weight-only)")
     ap.add_argument("--enable-prefix-caching", action="store_true",
                     help="share the cached K/V of equal leading prompt blocks across requests "
                          "(vLLM's flag; finished requests' blocks stay cached until evicted)")

@@ -91,6 +91,11 @@ hipError_t lumen_w4a8_decode_gemm(int, const void*, const float*, const void*, c
                                   hipStream_t);
 hipError_t lumen_w4_dequant(int, const void*, const void*, void*, long long, long long,
                             hipStream_t);
+hipError_t lumen_w4a16_gemv(int, const void*, const void*, const void*, void*, int, int, int,
+                            long long, long long, int, hipStream_t);
+hipError_t lumen_w4a16_decode_gemm(int, const void*, const void*, const void*, void*, float*, int*,
+                                   int, int, int, long long, long long, int, int, int,
+                                   hipStream_t);
 hipError_t lumen_mlp_gemm(int, int, const void*, long long, const void*, long long, void*, long long,
                           void*, long long, const void*, long long, int, int, int, int, int, float*,
                           int*, int, hipStream_t);
@@ -567,6 +572,78 @@ void w4_dequant(const at::Tensor& q, const at::Tensor& scale, at::Tensor& out) {
   check(lumen_w4_dequant(dcode(out), q.data_ptr(), scale.data_ptr(), out.data_ptr(), q.size(0),
                          out.size(1), cur_stream()),
         "w4_dequant");
+}
+
+// MXFP4 weight-only projections (kernels/w4a16_gemm.hip): x / y 16-bit, q / scale as above
+void need_w4a16(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale,
+                const at::Tensor& y, const char* what) {
+  if (!x.is_cuda() || x.dim() != 2)
+    throw std::invalid_argument(std::string("lumen: ") + what + " shape/layout/device mismatch");
+  need_w4(q, scale, x.size(1), what);
+  if (!y.is_cuda() || y.dim() != 2 || x.stride(1) != 1 || y.stride(1) != 1 ||
+      y.size(0) != x.size(0) || y.size(1) != q.size(0) || x.scalar_type() != y.scalar_type() ||
+      (x.scalar_type() != at::kBFloat16 && x.scalar_type() != at::kHalf) ||
+      x.device() != q.device() || y.device() != q.device())
+    throw std::invalid_argument(std::string("lumen: ") + what + " shape/layout/device mismatch");
+}
+
+// y [M, N] = x [M, K] @ wdq^T, 1 <= M <= 4.  cfg: 0, or 10 R + GS for one compiled (rows per wave
+// group, steps in flight) -- for lumen/bench/w4a16_bench.py
+void w4a16_gemv(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale, at::Tensor& y,
+                int64_t cfg) {
+  need_w4a16(x, q, scale, y, "w4a16_gemv");
+  if (x.size(0) < 1 || x.size(0) > 4 || q.size(0) % 4 != 0 || x.size(1) % 16 != 0 ||
+      x.stride(0) % 8 != 0 || x.stride(0) < x.size(1) || y.stride(0) < q.size(0))
+    throw std::invalid_argument("lumen: w4a16_gemv needs 1 <= M <= 4, N % 4 == 0, K % 16 == 0 and "
+                                "an x row stride >= K that is a multiple of 8");
+  if (cfg != 0 && cfg != 41 && cfg != 42 && cfg != 81 && cfg != 82)
+    throw std::invalid_argument("lumen: w4a16_gemv cfg must be 0, 41, 42, 81 or 82");
+  check(lumen_w4a16_gemv(dcode(x), x.data_ptr(), q.data_ptr(), scale.data_ptr(), y.data_ptr(),
+                         static_cast<int>(x.size(0)), static_cast<int>(q.size(0)),
+                         static_cast<int>(x.size(1)), x.stride(0), y.stride(0),
+                         static_cast<int>(cfg), cur_stream()),
+        "w4a16_gemv");
+}
+
+// the same product on the MFMA kernel with block tile (bm, bn) and split-K s (s > 1: ws f32
+// slabs + cnt zeroed tile counters), M <= bm
+void w4a16_decode_gemm(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale,
+                       at::Tensor& y, const std::optional<at::Tensor>& ws,
+                       const std::optional<at::Tensor>& cnt, int64_t bm, int64_t bn, int64_t s) {
+  need_w4a16(x, q, scale, y, "w4a16_decode_gemm");
+  const int64_t K = x.size(1), N = q.size(0);
+  const bool variant = ((bm == 64 || bm == 128) && (bn == 64 || bn == 128)) ||
+                       (bm == 256 && bn == 64);
+  if (!variant)
+    throw std::invalid_argument("lumen: w4a16_decode_gemm (bm, bn) must be one of (64, 64), "
+                                "(64, 128), (128, 64), (128, 128), (256, 64)");
+  if (x.size(0) < 1 || x.size(0) > bm)
+    throw std::invalid_argument("lumen: w4a16_decode_gemm needs 1 <= M <= bm");
+  if (K % 32 != 0 || N % 4 != 0 || x.stride(0) % 8 != 0 || x.stride(0) < K ||
+      y.stride(0) < N || y.stride(0) % 4 != 0)
+    throw std::invalid_argument("lumen: w4a16_decode_gemm needs K % 32 == 0, N % 4 == 0, an x row "
+                                "stride >= K that is a multiple of 8 and a y row stride that is "
+                                "a multiple of 4");
+  if (s < 1 || s > (K + 63) / 64)
+    throw std::invalid_argument("lumen: w4a16_decode_gemm needs 1 <= s <= ceil(K / 64)");
+  const long long tiles = (N + bn - 1) / bn;
+  if (s > 1) {
+    if (!ws || !cnt || !ws->is_cuda() || !cnt->is_cuda() || ws->device() != x.device() ||
+        cnt->device() != x.device() || !ws->is_contiguous() || !cnt->is_contiguous() ||
+        ws->scalar_type() != at::kFloat || cnt->scalar_type() != at::kInt)
+      throw std::invalid_argument("lumen: w4a16_decode_gemm split-K needs a contiguous f32 "
+                                  "workspace and int32 counters on x's device");
+    if (ws->numel() < tiles * s * bm * bn || cnt->numel() < tiles)
+      throw std::invalid_argument("lumen: w4a16_decode_gemm split-K workspace too small");
+  }
+  check(lumen_w4a16_decode_gemm(dcode(x), x.data_ptr(), q.data_ptr(), scale.data_ptr(),
+                                y.data_ptr(), s > 1 ? ws->data_ptr<float>() : nullptr,
+                                s > 1 ? cnt->data_ptr<int>() : nullptr,
+                                static_cast<int>(x.size(0)), static_cast<int>(N),
+                                static_cast<int>(K), x.stride(0), y.stride(0),
+                                static_cast<int>(bm), static_cast<int>(bn), static_cast<int>(s),
+                                cur_stream()),
+        "w4a16_decode_gemm");
 }
 
 // training-shape MLP GEMMs with the SwiGLU in the epilogue (kernels/mlp_gemm.hip):
@@ -1361,6 +1438,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("w8a8_gemm", &w8a8_gemm);
   m.def("w4a8_decode_gemm", &w4a8_decode_gemm);
   m.def("w4_dequant", &w4_dequant);
+  m.def("w4a16_gemv", &w4a16_gemv);
+  m.def("w4a16_decode_gemm", &w4a16_decode_gemm);
   m.def("mlp_gemm", &mlp_gemm, py::arg("epi"), py::arg("x"), py::arg("w"), py::arg("c"),
         py::arg("act") = py::none(), py::arg("gu") = py::none(), py::arg("group_m") = 4,
         py::arg("ws") = py::none(), py::arg("cnt") = py::none(), py::arg("split") = 0);

@@ -26,6 +26,7 @@
 // with zero nibbles (+0.0), whole 16-byte W chunks past that are zero-filled in registers with
 // scale 2^0.
 #include "common.h"
+#include "mxfp4.h"
 
 namespace lumen {
 namespace w4a8 {
@@ -345,22 +346,9 @@ hipError_t launch_dgemm(const void* xq, const float* sx, const void* W, const vo
 }
 
 // ---- dequantisation for the fallback -------------------------------------------------------------
-// 2^(e - 127) as f32: the byte is the exponent field (byte 0: the subnormal 2^-127)
-__device__ __forceinline__ float e8m0_f32(unsigned e) {
-  return __builtin_bit_cast(float, e ? e << 23 : 0x00400000u);
-}
-
-// the two e2m1 codes of byte B of v times s -> one packed 16-bit pair, exact
-template <typename T, int B> __device__ __forceinline__ unsigned cvt2(unsigned v, float s);
-#define LUMEN_W4_CVT(B)                                                                         \
-  template <> __device__ __forceinline__ unsigned cvt2<bf16, B>(unsigned v, float s) {          \
-    return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, s, B));    \
-  }                                                                                             \
-  template <> __device__ __forceinline__ unsigned cvt2<fp16, B>(unsigned v, float s) {          \
-    return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, s, B));     \
-  }
-LUMEN_W4_CVT(0) LUMEN_W4_CVT(1) LUMEN_W4_CVT(2) LUMEN_W4_CVT(3)
-#undef LUMEN_W4_CVT
+// (e8m0_f32 and cvt2, the block scale and the code-byte conversion, are kernels/mxfp4.h's)
+using mx::cvt2;
+using mx::e8m0_f32;
 
 // thread = 8 consecutive k of one row: one code word in, one 16-byte store out (K % 8 == 0)
 template <typename T>

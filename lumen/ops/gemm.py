@@ -550,6 +550,88 @@ def _linear_w4a8(x: torch.Tensor, w) -> torch.Tensor:
     return w4a8_fallback(xq, sx, w)
 
 
+# ---- MXFP4 weight-only (Mxfp4Weight.act is None, kernels/w4a16_gemm.hip) -------------------------
+# y = round(sum_k f32(x) f32(w.dequant())) on every route, no activation quantizer.  M <= 4: the
+# 4-bit rows-per-lane GEMV, always; 5 <= M <= 256: the W4A16 MFMA kernel where the measured plan
+# table (configs/kernels/w4a16_gemm_plans.json, written by lumen/bench/w4a16_bench.py) lists the
+# bucket; everything else -- prefill / mixed steps, shapes the kernels refuse -- w4_dequant into
+# the persistent 16-bit scratch and the 16-bit path unchanged.  LUMEN_W8=0 forces that fallback.
+W4A16_BMS = W8_BMS
+W4A16_BNS = {64: (64, 128), 128: (64, 128), 256: (64,)}   # compiled (BM, BN) variants
+W4A16_GEMV_CFGS = (41, 42, 81, 82)   # 10 R + GS: compiled (rows per wave group, steps in flight)
+_w4a16_plans: Optional[dict] = None
+
+
+def load_w4a16_plans(path: str) -> dict:
+    """{(N, K, BM): (BN, S)} from a plan file in w8_gemm_plans.json's format."""
+    return load_w8_plans(path)
+
+
+def w4a16_plans() -> dict:
+    """The shipped plan table (measured wins over the fallback only)."""
+    global _w4a16_plans
+    if _w4a16_plans is None:
+        _w4a16_plans = load_w4a16_plans(os.environ.get("LUMEN_W4A16_PLANS", os.path.join(
+            os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
+            "configs", "kernels", "w4a16_gemm_plans.json")))
+    return _w4a16_plans
+
+
+def w4a16_gemv_ok(x: torch.Tensor, w) -> bool:
+    return 0 < x.shape[0] <= 4 and _w8_common_ok(x, w) and w.shape[1] % 16 == 0
+
+
+def w4a16_plan(x: torch.Tensor, w) -> Optional[tuple]:
+    """(BM, BN, S) of the MFMA kernel for this call, None where it does not apply."""
+    if not (4 < x.shape[0] <= 256 and _w8_common_ok(x, w) and w.shape[1] % 32 == 0):
+        return None
+    bm = next(b for b in W4A16_BMS if x.shape[0] <= b)
+    p = w4a16_plans().get((w.shape[0], w.shape[1], bm))
+    return (bm,) + tuple(p) if p is not None else None
+
+
+def w4a16_gemv(x: torch.Tensor, w, out: Optional[torch.Tensor] = None, cfg: int = 0):
+    """y = x @ w.dequant()^T for 1 <= M <= 4 on the 4-bit GEMV (``cfg``: one of
+    ``W4A16_GEMV_CFGS`` instead of the measured default)."""
+    y = out if out is not None else torch.empty(x.shape[0], w.shape[0], device=x.device,
+                                                dtype=x.dtype)
+    native().w4a16_gemv(x, w.q, w.scale, y, cfg)
+    return y
+
+
+def w4a16_decode_gemm(x: torch.Tensor, w, bm: int, bn: int, s: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = x @ w.dequant()^T on the W4A16 MFMA kernel with block tile (bm, bn) and split-K s."""
+    y = out if out is not None else torch.empty(x.shape[0], w.shape[0], device=x.device,
+                                                dtype=x.dtype)
+    ws, cnt = _dg_splitk_ws(x.device, w.shape[0], bm, bn, s)
+    native().w4a16_decode_gemm(x, w.q, w.scale, y, ws, cnt, bm, bn, s)
+    return y
+
+
+def w4a16_fallback(x: torch.Tensor, w) -> torch.Tensor:
+    """The 16-bit path on W dequantised (bit-identical to ``w.dequant()``) into the scratch the
+    quantized modes share: the same function up to the library GEMM's accumulation order."""
+    return linear_nt(x, w4_dequant(w))
+
+
+def _linear_w4a16(x: torch.Tensor, w) -> torch.Tensor:
+    if not use_native(x):
+        return (x.float() @ w.dequant().float().t()).to(x.dtype)
+    if x.dtype != w.dtype:
+        raise ValueError(f"mxfp4 weight of a {w.dtype} model applied to {x.dtype} activations")
+    if x.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"activations {tuple(x.shape)} do not match the weight {tuple(w.shape)}")
+    if x.shape[0] == 0:
+        return x.new_empty(0, w.shape[0])
+    if W8 and w4a16_gemv_ok(x, w):
+        return w4a16_gemv(x, w)
+    p = w4a16_plan(x, w) if W8 else None
+    if p is not None:
+        return w4a16_decode_gemm(x, w, *p)
+    return w4a16_fallback(x, w)
+
+
 def _linear_w8(x: torch.Tensor, w) -> torch.Tensor:
     if w.act == "fp8":
         return _linear_w8a8(x, w)
@@ -575,10 +657,14 @@ def _linear_w8(x: torch.Tensor, w) -> torch.Tensor:
 def linear_nt(x: torch.Tensor, w) -> torch.Tensor:
     """x [M, K] @ w[N, K]^T -> [M, N]; ``w`` a 16-bit tensor, an fp8 ``QuantWeight`` (with
     ``act="fp8"``: the product of the per-token quantized x, ops/quant.py) or an ``Mxfp4Weight``
-    (always with the per-token quantized x)."""
+    (``act="fp8"``: with the per-token quantized x; ``act=None``: weight-only)."""
     if isinstance(w, QuantWeight):
         return _linear_w8(x, w)
     if isinstance(w, Mxfp4Weight):
+        if w.act is None:
+            return _linear_w4a16(x, w)
+        if w.act != "fp8":
+            raise ValueError(f"Mxfp4Weight.act must be None or 'fp8', got {w.act}")
         return _linear_w4a8(x, w)
     if skinny_ok(x, w):
         y = torch.empty(x.shape[0], w.shape[0], device=x.device, dtype=x.dtype)

@@ -1,6 +1,7 @@
 """Quantization for serving (``--quantization fp8`` weight-only, ``--quantization ptpc_fp8`` with
-per-token fp8 activations, ``--quantization mxfp4`` with MXFP4 weights and the same activations):
-the quantizers and the weight holders.
+per-token fp8 activations, ``--quantization mxfp4`` with MXFP4 weights and the same activations,
+``--quantization mxfp4_a16`` with MXFP4 weights and 16-bit activations): the quantizers and the
+weight holders.
 
 A projection weight ``w [N, K]`` is stored as OCP e4m3fn (``torch.float8_e4m3fn``, gfx950's fp8)
 with one f32 scale per output row; activations, accumulation and outputs keep their types.  The
@@ -81,11 +82,11 @@ def quantize_fp8_tokens(x: torch.Tensor):
     return xq, sx.contiguous()
 
 
-# ---- MXFP4 weights (--quantization mxfp4, W4A8) ---------------------------------------------------
+# ---- MXFP4 weights (--quantization mxfp4, W4A8; --quantization mxfp4_a16, W4A16) -----------------
 # OCP MX: blocks of 32 consecutive k share one E8M0 (power-of-two) scale, the elements are e2m1
 # (fp4: +-{0, .5, 1, 1.5, 2, 3, 4, 6}).  Round to nearest, no calibration.  The kernels that consume
 # it are in kernels/w4a8_gemm.hip: gfx950's scaled MFMA takes the codes and the block scales as they
-# are stored here.
+# are stored here; kernels/w4a16_gemm.hip converts them in registers for 16-bit activations.
 MX_BLOCK = 32
 E2M1_MAX = 6.0
 _E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
@@ -98,6 +99,10 @@ class Mxfp4Weight:
     scale: torch.Tensor   # [N, Kp / 32] uint8: biased E8M0 block exponents, 127 = 2^0
     K: int                # the true inner dimension
     dtype: torch.dtype    # model dtype of the activations and outputs
+    # "fp8": W4A8 (--quantization mxfp4), the activations are quantized per token row at run time
+    # (quantize_fp8_tokens).  None: weight-only (--quantization mxfp4_a16), the activations stay
+    # 16-bit: y = round(sum_k f32(x) f32(dequant())), kernels/w4a16_gemm.hip
+    act: Optional[str] = "fp8"
 
     @property
     def shape(self):

@@ -73,7 +73,8 @@ class EngineConfig:
     # and accumulation unchanged; "ptpc_fp8" = the same weights with the projection inputs
     # quantized to e4m3fn per token at run time (W8A8, vLLM's ptpc_fp8 on ROCm); "mxfp4" = MXFP4
     # weights (e2m1 + one E8M0 scale per 32 k, round to nearest) with the same per-token e4m3fn
-    # inputs (W4A8); embedding, norms and LM head stay 16-bit
+    # inputs (W4A8); "mxfp4_a16" = the same MXFP4 weights with the 16-bit activations unchanged
+    # (weight-only, W4A16); embedding, norms and LM head stay 16-bit
     quantization: Optional[str] = None
     # speculative decoding by prompt lookup (vLLM --speculative-model "[ngram]"): up to this many
     # draft tokens per greedy sequence, copied from where the sequence's last n tokens (n from
@@ -149,8 +150,9 @@ class LLMEngine:
 
             load_tuned_gemms()  # tuned hipBLASLt algorithms for the prefill/decode GEMM shapes
         dt = _DT[cfg.dtype] if dev.type == "cuda" else torch.float32
-        if cfg.quantization not in (None, "fp8", "ptpc_fp8", "mxfp4"):
-            raise ValueError("quantization must be None, 'fp8', 'ptpc_fp8' or 'mxfp4', got "
+        if cfg.quantization not in (None, "fp8", "ptpc_fp8", "mxfp4", "mxfp4_a16"):
+            raise ValueError("quantization must be None, 'fp8', 'ptpc_fp8', 'mxfp4' or "
+                             "'mxfp4_a16', got "
                              f"{cfg.quantization}")
         own_model = model is None   # a model passed in by the caller is left untouched
         if model is None:

@@ -52,7 +52,8 @@ class LayerW:
     ln1: torch.Tensor
     ln2: torch.Tensor
     qkv: torch.Tensor       # the four projections: 16-bit tensors, or ops.quant.QuantWeight
-    o: torch.Tensor         # under quantization="fp8" / "ptpc_fp8", Mxfp4Weight under "mxfp4"
+    o: torch.Tensor         # under quantization="fp8" / "ptpc_fp8", Mxfp4Weight under "mxfp4" /
+    #                         "mxfp4_a16"
     gate_up: torch.Tensor
     down: torch.Tensor
 
@@ -68,6 +69,8 @@ class ServeWeights:
     row-parallel rank its own K slice).  ``quantization="mxfp4"`` (W4A8): the four weights become
     ``Mxfp4Weight``s (e2m1 codes + one E8M0 scale per 32 consecutive k, a row-parallel rank forming
     the blocks over its own K slice) and the inputs are quantized as under ``ptpc_fp8``.
+    ``quantization="mxfp4_a16"`` (W4A16): the same ``Mxfp4Weight``s with ``act=None``, the inputs
+    stay 16-bit.
     Embedding, norms and the LM head stay 16-bit.
     ``release=True`` (the engine built the model itself) frees each layer's 16-bit projection
     storage as it goes."""
@@ -77,8 +80,9 @@ class ServeWeights:
         cfg: ModelConfig = model.config
         if cfg.arch != "llama":
             raise NotImplementedError("serving supports the Llama family")
-        if quantization not in (None, "fp8", "ptpc_fp8", "mxfp4"):
-            raise ValueError("quantization must be None, 'fp8', 'ptpc_fp8' or 'mxfp4', got "
+        if quantization not in (None, "fp8", "ptpc_fp8", "mxfp4", "mxfp4_a16"):
+            raise ValueError("quantization must be None, 'fp8', 'ptpc_fp8', 'mxfp4' or "
+                             "'mxfp4_a16', got "
                              f"{quantization}")
         self.cfg = cfg
         self.quantization = quantization
@@ -106,7 +110,8 @@ class ServeWeights:
                     from ..ops.gemm import w8_reserve
                     from ..ops.quant import quantize_fp8_rows, quantize_mxfp4_rows
 
-                    quantize = quantize_mxfp4_rows if quantization == "mxfp4" else quantize_fp8_rows
+                    quantize = (quantize_mxfp4_rows if quantization in ("mxfp4", "mxfp4_a16")
+                                else quantize_fp8_rows)
                     if qkv.is_cuda:
                         for name, t in (("q|k|v", qkv), ("o", o), ("gate|up", gu), ("down", dn)):
                             # kernels/w8_gemm.hip (the dequant fallback included) moves the
@@ -120,6 +125,9 @@ class ServeWeights:
                     if quantization == "ptpc_fp8":
                         for t in (qkv, o, gu, dn):
                             t.act = "fp8"
+                    elif quantization == "mxfp4_a16":
+                        for t in (qkv, o, gu, dn):
+                            t.act = None
                     if qkv.q.is_cuda:
                         # the dequant fallback's scratch is sized once, for the largest projection
                         w8_reserve(qkv.q.device, max(t.shape[0] * t.shape[1]
