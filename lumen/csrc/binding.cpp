@@ -272,6 +272,21 @@ void skinny_gemm(const at::Tensor& x, const at::Tensor& w, at::Tensor& y) {
         "skinny_gemm");
 }
 
+// split-K (s > 1) arguments of the decode-GEMM family (kernels/dgemm.h): f32 slabs for ``tiles``
+// output tiles x s slices of a [bm, bn] block tile and one zeroed int32 ticket counter per tile
+void need_splitk(const std::optional<at::Tensor>& ws, const std::optional<at::Tensor>& cnt,
+                 const at::Tensor& x, long long tiles, int64_t s, int64_t bm, int64_t bn,
+                 const char* what) {
+  if (s <= 1) return;
+  if (!ws || !cnt || !ws->is_cuda() || !cnt->is_cuda() || ws->device() != x.device() ||
+      cnt->device() != x.device() || !ws->is_contiguous() || !cnt->is_contiguous() ||
+      ws->scalar_type() != at::kFloat || cnt->scalar_type() != at::kInt)
+    throw std::invalid_argument(std::string("lumen: ") + what + " split-K needs a contiguous f32 "
+                                "workspace and int32 counters on the activations' device");
+  if (ws->numel() < tiles * s * bm * bn || cnt->numel() < tiles)
+    throw std::invalid_argument(std::string("lumen: ") + what + " split-K workspace too small");
+}
+
 // decode-batch MFMA GEMM (kernels/decode_gemm.hip): y = x @ w^T with block tile (bm, bn) and
 // split-K s (s > 1: ws f32 slabs + cnt zeroed tile counters)
 void decode_gemm(const at::Tensor& x, const at::Tensor& w, at::Tensor& y,
@@ -289,13 +304,7 @@ void decode_gemm(const at::Tensor& x, const at::Tensor& w, at::Tensor& y,
       y.size(1) != w.size(0) || x.scalar_type() != w.scalar_type() ||
       y.scalar_type() != w.scalar_type())
     throw std::invalid_argument("lumen: decode_gemm shape/layout mismatch");
-  const long long tiles = (w.size(0) + bn - 1) / bn;
-  if (s > 1) {
-    if (!ws || !cnt || !ws->is_cuda() || !cnt->is_cuda() ||
-        ws->scalar_type() != at::kFloat || cnt->scalar_type() != at::kInt ||
-        ws->numel() < tiles * s * bm * bn || cnt->numel() < tiles)
-      throw std::invalid_argument("lumen: decode_gemm split-K workspace too small");
-  }
+  need_splitk(ws, cnt, x, (w.size(0) + bn - 1) / bn, s, bm, bn, "decode_gemm");
   check(lumen_decode_gemm(dcode(w), x.data_ptr(), w.data_ptr(), y.data_ptr(),
                           s > 1 ? ws->data_ptr<float>() : nullptr,
                           s > 1 ? cnt->data_ptr<int>() : nullptr, static_cast<int>(y.size(0)),
@@ -359,16 +368,7 @@ void w8_decode_gemm(const at::Tensor& x, const at::Tensor& q, const at::Tensor& 
                                 "a multiple of 4");
   if (s < 1 || s > q.size(1) / 64)
     throw std::invalid_argument("lumen: w8_decode_gemm needs 1 <= s <= K / 64");
-  const long long tiles = (q.size(0) + bn - 1) / bn;
-  if (s > 1) {
-    if (!ws || !cnt || !ws->is_cuda() || !cnt->is_cuda() || ws->device() != x.device() ||
-        cnt->device() != x.device() || !ws->is_contiguous() || !cnt->is_contiguous() ||
-        ws->scalar_type() != at::kFloat || cnt->scalar_type() != at::kInt)
-      throw std::invalid_argument("lumen: w8_decode_gemm split-K needs a contiguous f32 "
-                                  "workspace and int32 counters on x's device");
-    if (ws->numel() < tiles * s * bm * bn || cnt->numel() < tiles)
-      throw std::invalid_argument("lumen: w8_decode_gemm split-K workspace too small");
-  }
+  need_splitk(ws, cnt, x, (q.size(0) + bn - 1) / bn, s, bm, bn, "w8_decode_gemm");
   check(lumen_w8_decode_gemm(dcode(x), x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(),
                              y.data_ptr(), s > 1 ? ws->data_ptr<float>() : nullptr,
                              s > 1 ? cnt->data_ptr<int>() : nullptr, static_cast<int>(x.size(0)),
@@ -463,16 +463,7 @@ void w8a8_decode_gemm(const at::Tensor& xq, const at::Tensor& sx, const at::Tens
   if (form != 0 && form != 1)
     throw std::invalid_argument("lumen: w8a8_decode_gemm form must be 0 (scaled K = 128 MFMA) or "
                                 "1 (non-scaled K = 32 MFMA)");
-  const long long tiles = (q.size(0) + bn - 1) / bn;
-  if (s > 1) {
-    if (!ws || !cnt || !ws->is_cuda() || !cnt->is_cuda() || ws->device() != xq.device() ||
-        cnt->device() != xq.device() || !ws->is_contiguous() || !cnt->is_contiguous() ||
-        ws->scalar_type() != at::kFloat || cnt->scalar_type() != at::kInt)
-      throw std::invalid_argument("lumen: w8a8_decode_gemm split-K needs a contiguous f32 "
-                                  "workspace and int32 counters on xq's device");
-    if (ws->numel() < tiles * s * bm * bn || cnt->numel() < tiles)
-      throw std::invalid_argument("lumen: w8a8_decode_gemm split-K workspace too small");
-  }
+  need_splitk(ws, cnt, xq, (q.size(0) + bn - 1) / bn, s, bm, bn, "w8a8_decode_gemm");
   check(lumen_w8a8_decode_gemm(dcode(y), xq.data_ptr(), sx.data_ptr<float>(), q.data_ptr(),
                                scale.data_ptr<float>(), y.data_ptr(),
                                s > 1 ? ws->data_ptr<float>() : nullptr,
@@ -539,16 +530,7 @@ void w4a8_decode_gemm(const at::Tensor& xq, const at::Tensor& sx, const at::Tens
   if (xq.size(0) > bm) throw std::invalid_argument("lumen: w4a8_decode_gemm needs 1 <= M <= bm");
   if (s < 1 || s > (K + 127) / 128)
     throw std::invalid_argument("lumen: w4a8_decode_gemm needs 1 <= s <= ceil(K / 128)");
-  const long long tiles = (N + bn - 1) / bn;
-  if (s > 1) {
-    if (!ws || !cnt || !ws->is_cuda() || !cnt->is_cuda() || ws->device() != xq.device() ||
-        cnt->device() != xq.device() || !ws->is_contiguous() || !cnt->is_contiguous() ||
-        ws->scalar_type() != at::kFloat || cnt->scalar_type() != at::kInt)
-      throw std::invalid_argument("lumen: w4a8_decode_gemm split-K needs a contiguous f32 "
-                                  "workspace and int32 counters on xq's device");
-    if (ws->numel() < tiles * s * bm * bn || cnt->numel() < tiles)
-      throw std::invalid_argument("lumen: w4a8_decode_gemm split-K workspace too small");
-  }
+  need_splitk(ws, cnt, xq, (N + bn - 1) / bn, s, bm, bn, "w4a8_decode_gemm");
   check(lumen_w4a8_decode_gemm(dcode(y), xq.data_ptr(), sx.data_ptr<float>(), q.data_ptr(),
                                scale.data_ptr(), y.data_ptr(),
                                s > 1 ? ws->data_ptr<float>() : nullptr,
@@ -626,16 +608,7 @@ void w4a16_decode_gemm(const at::Tensor& x, const at::Tensor& q, const at::Tenso
                                 "a multiple of 4");
   if (s < 1 || s > (K + 63) / 64)
     throw std::invalid_argument("lumen: w4a16_decode_gemm needs 1 <= s <= ceil(K / 64)");
-  const long long tiles = (N + bn - 1) / bn;
-  if (s > 1) {
-    if (!ws || !cnt || !ws->is_cuda() || !cnt->is_cuda() || ws->device() != x.device() ||
-        cnt->device() != x.device() || !ws->is_contiguous() || !cnt->is_contiguous() ||
-        ws->scalar_type() != at::kFloat || cnt->scalar_type() != at::kInt)
-      throw std::invalid_argument("lumen: w4a16_decode_gemm split-K needs a contiguous f32 "
-                                  "workspace and int32 counters on x's device");
-    if (ws->numel() < tiles * s * bm * bn || cnt->numel() < tiles)
-      throw std::invalid_argument("lumen: w4a16_decode_gemm split-K workspace too small");
-  }
+  need_splitk(ws, cnt, x, (N + bn - 1) / bn, s, bm, bn, "w4a16_decode_gemm");
   check(lumen_w4a16_decode_gemm(dcode(x), x.data_ptr(), q.data_ptr(), scale.data_ptr(),
                                 y.data_ptr(), s > 1 ? ws->data_ptr<float>() : nullptr,
                                 s > 1 ? cnt->data_ptr<int>() : nullptr,

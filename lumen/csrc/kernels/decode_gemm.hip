@@ -20,41 +20,21 @@
 //  * the product is formed transposed, y^T = W x^T (v_mfma_f32_16x16x32_{bf16,f16}: W rows are
 //    the A operand, x rows the B operand), so a lane's four accumulators are four consecutive
 //    output columns of one row: 8-byte stores;
-//  * split-K (S > 1) is reduced IN the launch: every slice writes its f32 slab, takes a ticket
-//    on the tile's counter (agent-scope release), and the last arriver (agent-scope acquire) sums
-//    the other slabs into its registers and stores the tile.  Slices of a tile are mapped to
-//    neighbouring virtual block ids under the XCD-aware remap, so they share an XCD.
+//  * split-K (S > 1) is reduced in the launch and the blocks are mapped to (tile, slice) under
+//    the XCD-aware remap: see dgemm.h.
 #include "common.h"
+#include "dgemm.h"
 
 namespace lumen {
 namespace dg {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct Mfma;
-template <> struct Mfma<bf16> {
-  static __device__ __forceinline__ f32x4 run(uint4 a, uint4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mfma<fp16> {
-  static __device__ __forceinline__ f32x4 run(uint4 a, uint4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a),
-                                                  __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-};
+using dgemm::f32x4;
+using dgemm::Mfma;
+using dgemm::swz;
 
 constexpr int BK = 64;      // k elements per stage = one 128-byte image row per matrix row
 constexpr int ROWB = 128;
 constexpr int NSTAGE = 3;
-
-// 16-byte chunk c of image row r lives at chunk c ^ swz(r): a ds_read_b128 fragment read (16
-// rows at one chunk, lane groups of 16) then touches 16 distinct 16-byte bank slots (rows of
-// either parity share the 256-byte bank row's halves; the XOR spreads the 8 row pairs)
-__device__ __forceinline__ int swz(int r) { return (r >> 1) & 7; }
 
 template <int N>
 __device__ __forceinline__ void wait_vm() {
@@ -156,19 +136,13 @@ dgemm_kernel(const T* __restrict__ x, const T* __restrict__ W, T* __restrict__ y
   __shared__ __attribute__((aligned(16))) char lds[NSTAGE * STAGE_B + 16];
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // XCD-aware bijective remap (blocks round-robin over 8 XCDs): consecutive virtual ids -- the
-  // S slices of one tile, then the next tile -- land on one XCD
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nb >> 3, r8 = nb & 7;
-  const int v = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int tile = v / S, slice = v - tile * S;
+  const dgemm::TileSlice ts = dgemm::tile_slice(blockIdx.x, gridDim.x, S);
+  const int tile = ts.tile, slice = ts.slice;
   const int tn = tile % tiles_n;
   const int n0 = tn * BN;
   const int nvalid = min(BN, N - n0);
-  // k64 tiles of this slice: an even share, the first (kt_total % S) slices one more
-  const int per = kt_total / S, extra = kt_total - per * S;
-  const int kb = slice * per + min(slice, extra);
-  const int nk = per + (slice < extra ? 1 : 0);
+  const dgemm::KSlice ks = dgemm::k_slice(slice, S, kt_total);
+  const int kb = ks.kb, nk = ks.nk;
   const T* Wt = W + (long long)n0 * K;
   const int wm = wid / WN, wn = wid - (wid / WN) * WN;
   const int nrow0 = wn * (BN / WN), mrow0 = BN + wm * (BM / WM);
@@ -200,43 +174,8 @@ dgemm_kernel(const T* __restrict__ x, const T* __restrict__ W, T* __restrict__ y
     buf = buf == 2 ? 0 : buf + 1;
   }
 
-  if (S > 1) {
-    // slab of this slice: register-major, one 1-KiB wave-instruction per accumulator tile
-    float* slab = ws + ((long long)tile * S + slice) * (NT * NI * MJ * 4);
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < MJ; ++j)
-        *reinterpret_cast<f32x4*>(slab + ((i * MJ + j) * NT + threadIdx.x) * 4) = acc[i][j];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int* flag = reinterpret_cast<int*>(lds + NSTAGE * STAGE_B);
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const int old = __hip_atomic_fetch_add(cnt + tile, 1, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-      const int last = old == S - 1;
-      if (last) __hip_atomic_store(cnt + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *flag = last;
-    }
-    __syncthreads();
-    if (!*flag) return;
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    for (int o = 0; o < S; ++o) {
-      if (o == slice) continue;
-      const float* os = ws + ((long long)tile * S + o) * (NT * NI * MJ * 4);
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int j = 0; j < MJ; ++j)
-          acc[i][j] += *reinterpret_cast<const f32x4*>(os + ((i * MJ + j) * NT + threadIdx.x) * 4);
-    }
-  }
+  LUMEN_DGEMM_SPLITK_REDUCE_OR_RETURN(NT, NI, MJ, acc, ws, cnt, tile, slice, S,
+                                      reinterpret_cast<int*>(lds + NSTAGE * STAGE_B));
 
   // lane holds y^T[n = n0 + nrow0 + 16 i + 4 (lane >> 4) + 0..3][m = mrow0 - BN + 16 j + (lane & 15)]
   const int lr = lane & 15, lg = lane >> 4;

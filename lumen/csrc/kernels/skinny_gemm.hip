@@ -15,27 +15,16 @@
 //    traffic going at one workgroup per CU;
 //  * the four K partials meet in LDS; wave 0 writes the M x 16 output tile.
 #include "common.h"
+#include "dgemm.h"
+#include "gemv.h"
 
 namespace lumen {
 namespace sk {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct Mfma;
-template <> struct Mfma<bf16> {
-  static __device__ __forceinline__ f32x4 run(uint4 a, uint4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mfma<fp16> {
-  static __device__ __forceinline__ f32x4 run(uint4 a, uint4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a),
-                                                  __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-};
+using dgemm::f32x4;
+using dgemm::Mfma;
+using gemv::dot2;
+using gemv::sum16;
 
 constexpr int U = 8;  // k-steps (of 32) per pipeline stage
 
@@ -115,32 +104,7 @@ __global__ void __launch_bounds__(256) skinny_kernel(const T* __restrict__ x,
 // which measured 2.3-3.4 TB/s.  Here a wave-instruction reads 4 rows x 256 contiguous bytes
 // (lane: row L >> 4, 16-byte chunk L & 15), the full-rate access shape, and v_dot2c_f32_bf16
 // does the (at most 4 rows x 2 FLOP/byte) arithmetic.
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-template <typename T> __device__ __forceinline__ float dot2(unsigned a, unsigned b, float c);
-template <> __device__ __forceinline__ float dot2<bf16>(unsigned a, unsigned b, float c) {
-  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a),
-                                         __builtin_bit_cast(bf16x2, b), c, false);
-}
-template <> __device__ __forceinline__ float dot2<fp16>(unsigned a, unsigned b, float c) {
-  return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b), c,
-                                false);
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL,
-                                                               0xF, 0xF, false));
-}
-__device__ __forceinline__ float sum16(float v) {  // over the 16 lanes of a DPP row
-  v += dppf<0xB1>(v);
-  v += dppf<0x4E>(v);
-  v += dppf<0x141>(v);
-  v += dppf<0x140>(v);
-  return v;
-}
-
+// (dot2 and the DPP row sum sum16 are gemv.h's)
 constexpr int GU = 8;  // 128-element steps in flight per wave
 
 // SWIGLU: x is the fused gate|up GEMM output [M, 2K] and the operand is act = silu(gate) * up,

@@ -21,64 +21,31 @@
 // k = k0 + 16 g + 8 s + j -- the permutation of kernels/w8_gemm.hip -- and x's B operand is read
 // from LDS at the same k (16-byte chunk 2 g + s of the stage).
 #include "common.h"
+#include "dgemm.h"
+#include "gemv.h"
 #include "mxfp4.h"
 
 namespace lumen {
 namespace w4a16 {
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
+using dgemm::f32x4;
+using dgemm::ld16z;
+using dgemm::Mfma;
+using dgemm::ntld16z;
+using dgemm::swz;
+using gemv::dot2;
+using gemv::sum16;
 using mx::cvt2;
 using mx::cvt8;
 using mx::e8m0_f32;
 
-// weights are read exactly once per step: non-temporal, so they do not evict x / y.  Where not
-// ``ok`` nothing is read: zero codes (+0.0) with scale 2^0 (byte 0xff would be NaN)
-__device__ __forceinline__ uint4 ntld16z(const unsigned char* p, bool ok) {
-  uint4 r = make_uint4(0, 0, 0, 0);
-  if (ok)
-    r = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)));
-  return r;
-}
+// a block's E8M0 byte where ``ok``, 2^0 elsewhere (0xff would be NaN; the codes that go with it
+// are dgemm.h's ntld16z zeros, +0.0)
 __device__ __forceinline__ unsigned ntld1s(const unsigned char* p, bool ok) {
   unsigned r = 0x7f;
   if (ok) r = __builtin_nontemporal_load(p);
   return r;
-}
-template <typename T>
-__device__ __forceinline__ uint4 ld16z(const T* p, bool ok) {
-  uint4 r = make_uint4(0, 0, 0, 0);
-  if (ok) r = *reinterpret_cast<const uint4*>(p);
-  return r;
-}
-
-template <typename T> __device__ __forceinline__ float dot2(unsigned a, unsigned b, float c);
-template <> __device__ __forceinline__ float dot2<bf16>(unsigned a, unsigned b, float c) {
-  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a),
-                                         __builtin_bit_cast(bf16x2, b), c, false);
-}
-template <> __device__ __forceinline__ float dot2<fp16>(unsigned a, unsigned b, float c) {
-  return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b), c,
-                                false);
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL,
-                                                               0xF, 0xF, false));
-}
-__device__ __forceinline__ float sum16(float v) {  // over the 16 lanes of a DPP row
-  v += dppf<0xB1>(v);
-  v += dppf<0x4E>(v);
-  v += dppf<0x141>(v);
-  v += dppf<0x140>(v);
-  return v;
 }
 
 // ---- 1 <= M <= 4: rows-per-lane GEMV -----------------------------------------------------------
@@ -199,28 +166,11 @@ w4a16_gemv_kernel(const T* __restrict__ x, const unsigned char* __restrict__ W,
 //    stages: x chunks past K (K % 32 == 0: the last stage may be half a stage) and past the
 //    slice's last stage are masked to zero on their way to LDS, and the W words that meet them
 //    re-read the row's last block (finite codes, times zero).
-//  * split-K is reduced in the launch (f32 slabs + one agent-scope ticket per tile); the last
-//    arriver stores the tile and leaves the ticket zero.
-template <typename T> struct Mfma;
-template <> struct Mfma<bf16> {
-  static __device__ __forceinline__ f32x4 run(uint4 a, uint4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mfma<fp16> {
-  static __device__ __forceinline__ f32x4 run(uint4 a, uint4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a),
-                                                  __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-};
-
+//  * split-K: see dgemm.h.
 constexpr int BK = 64;     // k elements per stage: one 128-byte LDS row per x row, 32 W bytes
 constexpr int ROWB = 128;
 constexpr int PD = 8;      // k64 stages of W in flight per wave (8 bytes per lane and stage)
 constexpr int NT = 256;
-
-__device__ __forceinline__ int swz(int r) { return (r >> 1) & 7; }
 
 template <typename T, int BM, int BN>
 __global__ void __launch_bounds__(NT, 1)
@@ -239,18 +189,12 @@ w4a16_dgemm_kernel(const T* __restrict__ x, const unsigned char* __restrict__ W,
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lr = lane & 15, lg = lane >> 4;
-  // XCD-aware bijective remap (blocks round-robin over 8 XCDs): consecutive virtual ids -- the
-  // S slices of one tile, then the next tile -- land on one XCD
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nb >> 3, r8 = nb & 7;
-  const int v = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int tile = v / S, slice = v - tile * S;
+  const dgemm::TileSlice ts = dgemm::tile_slice(blockIdx.x, gridDim.x, S);
+  const int tile = ts.tile, slice = ts.slice;
   const int n0 = tile * BN;
   const int nvalid = min(BN, N - n0);
-  // k64 stages of this slice: an even share, the first (kt_total % S) slices one more
-  const int per = kt_total / S, extra = kt_total - per * S;
-  const int kb = slice * per + min(slice, extra);
-  const int nk = per + (slice < extra ? 1 : 0);
+  const dgemm::KSlice ks = dgemm::k_slice(slice, S, kt_total);
+  const int kb = ks.kb, nk = ks.nk;
   const int nrow0 = wid * (BN / 4);
   const int KB = K >> 5;  // blocks per W row (K % 32 == 0)
 
@@ -359,43 +303,8 @@ w4a16_dgemm_kernel(const T* __restrict__ x, const unsigned char* __restrict__ W,
       }
   }
 
-  if (S > 1) {
-    // slab of this slice: register-major, one 1-KiB wave-instruction per accumulator tile
-    float* slab = ws + ((long long)tile * S + slice) * (NT * NI * MJ * 4);
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < MJ; ++j)
-        *reinterpret_cast<f32x4*>(slab + ((i * MJ + j) * NT + threadIdx.x) * 4) = acc[i][j];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int* flag = reinterpret_cast<int*>(lds + 2 * STAGE_B);
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const int old = __hip_atomic_fetch_add(cnt + tile, 1, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-      const int last = old == S - 1;
-      if (last) __hip_atomic_store(cnt + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *flag = last;
-    }
-    __syncthreads();
-    if (!*flag) return;
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    for (int o = 0; o < S; ++o) {
-      if (o == slice) continue;
-      const float* os = ws + ((long long)tile * S + o) * (NT * NI * MJ * 4);
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int j = 0; j < MJ; ++j)
-          acc[i][j] += *reinterpret_cast<const f32x4*>(os + ((i * MJ + j) * NT + threadIdx.x) * 4);
-    }
-  }
+  LUMEN_DGEMM_SPLITK_REDUCE_OR_RETURN(NT, NI, MJ, acc, ws, cnt, tile, slice, S,
+                                      reinterpret_cast<int*>(lds + 2 * STAGE_B));
 
   // lane holds y^T[n = n0 + nrow0 + 16 i + 4 (lane >> 4) + 0..3][m = 16 j + (lane & 15)]
 #pragma unroll

@@ -26,29 +26,18 @@
 // with zero nibbles (+0.0), whole 16-byte W chunks past that are zero-filled in registers with
 // scale 2^0.
 #include "common.h"
+#include "dgemm.h"
 #include "mxfp4.h"
 
 namespace lumen {
 namespace w4a8 {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+using dgemm::f32x4;
+using dgemm::ld16z;
+using dgemm::ntld16z;
+using dgemm::swz;
 
-// weights are read exactly once per step: non-temporal, so they do not evict x / y
-__device__ __forceinline__ uint4 ntld16z(const unsigned char* p, bool ok) {
-  uint4 r = make_uint4(0, 0, 0, 0);
-  if (ok)
-    r = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)));
-  return r;
-}
-__device__ __forceinline__ uint4 ld16z(const unsigned char* p, bool ok) {
-  uint4 r = make_uint4(0, 0, 0, 0);
-  if (ok) r = *reinterpret_cast<const uint4*>(p);
-  return r;
-}
 // a block's E8M0 byte where ``ok``, 2^0 elsewhere (0xff would be NaN)
 __device__ __forceinline__ int ntld1s(const unsigned char* p, bool ok) {
   int r = 0x7f;
@@ -71,9 +60,6 @@ constexpr int ROWB = 128;
 constexpr int NT = 256;
 constexpr int XP = 16;     // BM = 16: k128 steps of x per LDS panel
 
-// 16-byte chunk c of LDS row r sits at chunk c ^ swz(r) (kernels/w8a8_gemm.hip's swizzle)
-__device__ __forceinline__ int swz(int r) { return (r >> 1) & 7; }
-
 // Block tile = BM rows (the padded decode batch) x BN output columns x a K range (split-K S), 4
 // waves; y^T = W xq^T, so a lane's four accumulators are four consecutive output columns.
 //  * wave w owns columns [w BN / 4, (w + 1) BN / 4); per k128 step a lane loads the 16 bytes
@@ -86,8 +72,8 @@ __device__ __forceinline__ int swz(int r) { return (r >> 1) & 7; }
 //    32-step panel -- 16 KiB in flight per wave -- was 1-7 us slower at every 7B projection and
 //    twice as slow with split-K: the per-workgroup start-up, not the depth of the stream, is
 //    what costs.)
-//  * split-K is reduced in the launch (f32 slabs + one agent-scope ticket per tile); whoever
-//    stores the tile -- with split-K the last arriver -- applies sx[m].
+//  * split-K: see dgemm.h; whoever stores the tile -- with split-K the last arriver -- applies
+//    sx[m].
 template <typename T, int BM, int BN>
 __global__ void __launch_bounds__(NT, 1)
 w4a8_dgemm_kernel(const unsigned char* __restrict__ xq, const float* __restrict__ sx,
@@ -105,18 +91,12 @@ w4a8_dgemm_kernel(const unsigned char* __restrict__ xq, const float* __restrict_
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lr = lane & 15, lg = lane >> 4;
-  // XCD-aware bijective remap (blocks round-robin over 8 XCDs): consecutive virtual ids -- the
-  // S slices of one tile, then the next tile -- land on one XCD
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nb >> 3, r8 = nb & 7;
-  const int v = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int tile = v / S, slice = v - tile * S;
+  const dgemm::TileSlice ts = dgemm::tile_slice(blockIdx.x, gridDim.x, S);
+  const int tile = ts.tile, slice = ts.slice;
   const int n0 = tile * BN;
   const int nvalid = min(BN, N - n0);
-  // k128 tiles of this slice: an even share, the first (kt_total % S) slices one more
-  const int per = kt_total / S, extra = kt_total - per * S;
-  const int kb = slice * per + min(slice, extra);
-  const int nk = per + (slice < extra ? 1 : 0);
+  const dgemm::KSlice ks = dgemm::k_slice(slice, S, kt_total);
+  const int kb = ks.kb, nk = ks.nk;
   const int nrow0 = wid * (BN / 4);
   const int KB = (K + 31) >> 5;  // blocks per W row: 16 code bytes and one scale byte each
 
@@ -267,43 +247,8 @@ w4a8_dgemm_kernel(const unsigned char* __restrict__ xq, const float* __restrict_
     }
   }
 
-  if (S > 1) {
-    // slab of this slice: register-major, one 1-KiB wave-instruction per accumulator tile
-    float* slab = ws + ((long long)tile * S + slice) * (NT * NI * MJ * 4);
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < MJ; ++j)
-        *reinterpret_cast<f32x4*>(slab + ((i * MJ + j) * NT + threadIdx.x) * 4) = acc[i][j];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int* flag = reinterpret_cast<int*>(lds + LDS_B);
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const int old = __hip_atomic_fetch_add(cnt + tile, 1, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-      const int last = old == S - 1;
-      if (last) __hip_atomic_store(cnt + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *flag = last;
-    }
-    __syncthreads();
-    if (!*flag) return;
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    for (int o = 0; o < S; ++o) {
-      if (o == slice) continue;
-      const float* os = ws + ((long long)tile * S + o) * (NT * NI * MJ * 4);
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int j = 0; j < MJ; ++j)
-          acc[i][j] += *reinterpret_cast<const f32x4*>(os + ((i * MJ + j) * NT + threadIdx.x) * 4);
-    }
-  }
+  LUMEN_DGEMM_SPLITK_REDUCE_OR_RETURN(NT, NI, MJ, acc, ws, cnt, tile, slice, S,
+                                      reinterpret_cast<int*>(lds + LDS_B));
 
   // lane holds y^T[n = n0 + nrow0 + 16 i + 4 (lane >> 4) + 0..3][m = 16 j + (lane & 15)]
 #pragma unroll

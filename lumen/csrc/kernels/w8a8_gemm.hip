@@ -24,36 +24,32 @@
 // it with exact integer data).  K % 16 == 0: 16-byte chunks past K are zero-filled in registers /
 // LDS (a zero byte is 0.0 in e4m3).
 #include "common.h"
+#include "dgemm.h"
+#include "gemv.h"
 
 namespace lumen {
 namespace w8a8 {
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using dgemm::f32x4;
+using dgemm::ld16z;
+using dgemm::ntload16;
+using dgemm::swz;
+using gemv::cvt2;
+using gemv::dot2;
+using gemv::sum16;
 
-constexpr float kFp8Max = 448.f;
-constexpr float kTiny = 1e-12f;
-
-// weights are read exactly once per step: non-temporal, so they do not evict x / y
-__device__ __forceinline__ uint4 ntload16(const unsigned char* p) {
-  return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)));
-}
-
-// a 16-byte load where ``ok``, zeros elsewhere (chunks past K, steps past a slice)
-__device__ __forceinline__ uint4 ld16z(const unsigned char* p, bool ok) {
-  uint4 r = make_uint4(0, 0, 0, 0);
-  if (ok) r = *reinterpret_cast<const uint4*>(p);
-  return r;
-}
+// dgemm::ntld16z, kept here through ntload16 as this file always had it: with the header's form
+// (the load written out) w8a8_gemv_kernel<*, 2, 8, 1> takes 83 VGPRs for 76, a wave per SIMD less
 __device__ __forceinline__ uint4 ntld16z(const unsigned char* p, bool ok) {
   uint4 r = make_uint4(0, 0, 0, 0);
   if (ok) r = ntload16(p);
   return r;
 }
+
+constexpr float kFp8Max = 448.f;
+constexpr float kTiny = 1e-12f;
 
 // ---- per-token activation quantisation -----------------------------------------------------------
 // One workgroup per row; a thread owns 16-element chunks (two 16-byte loads, one 16-byte store).
@@ -144,49 +140,11 @@ act_quant_kernel(const T* __restrict__ x, unsigned char* __restrict__ xq, float*
 }
 
 // ---- 1 <= M <= 4: rows-per-lane GEMV -------------------------------------------------------------
-// two e4m3fn bytes of v (HI: bytes 2, 3; else bytes 0, 1) -> one packed 16-bit pair, exact
-template <typename T, bool HI> __device__ __forceinline__ unsigned cvt2(unsigned v);
-template <> __device__ __forceinline__ unsigned cvt2<bf16, false>(unsigned v) {
-  return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v, 1.0f, false));
-}
-template <> __device__ __forceinline__ unsigned cvt2<bf16, true>(unsigned v) {
-  return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v, 1.0f, true));
-}
-template <> __device__ __forceinline__ unsigned cvt2<fp16, false>(unsigned v) {
-  return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(v, 1.0f, false));
-}
-template <> __device__ __forceinline__ unsigned cvt2<fp16, true>(unsigned v) {
-  return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(v, 1.0f, true));
-}
-
-template <typename T> __device__ __forceinline__ float dot2(unsigned a, unsigned b, float c);
-template <> __device__ __forceinline__ float dot2<bf16>(unsigned a, unsigned b, float c) {
-  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a),
-                                         __builtin_bit_cast(bf16x2, b), c, false);
-}
-template <> __device__ __forceinline__ float dot2<fp16>(unsigned a, unsigned b, float c) {
-  return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b), c,
-                                false);
-}
-
 // 4 fp8 weights . 4 fp8 activations (one word each)
 template <typename T>
 __device__ __forceinline__ float dot4(unsigned w, unsigned x, float c) {
   c = dot2<T>(cvt2<T, false>(w), cvt2<T, false>(x), c);
   return dot2<T>(cvt2<T, true>(w), cvt2<T, true>(x), c);
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL,
-                                                               0xF, 0xF, false));
-}
-__device__ __forceinline__ float sum16(float v) {  // over the 16 lanes of a DPP row
-  v += dppf<0xB1>(v);
-  v += dppf<0x4E>(v);
-  v += dppf<0x141>(v);
-  v += dppf<0x140>(v);
-  return v;
 }
 
 // lane = one 16-byte chunk (16 k elements) of each of R weight rows and of each x row; one
@@ -284,10 +242,6 @@ constexpr int ROWB = 128;
 constexpr int PD = 2;      // k128 steps of W in flight per wave (decode kernel)
 constexpr int NT = 256;
 
-// 16-byte chunk c of LDS row r sits at chunk c ^ swz(r): the 16 rows x 4 lane groups of one
-// fragment read spread over all banks (kernels/decode_gemm.hip's swizzle, here on fp8 rows)
-__device__ __forceinline__ int swz(int r) { return (r >> 1) & 7; }
-
 // ---- 5 <= M <= 256 -------------------------------------------------------------------------------
 // Block tile = BM rows (the padded decode batch) x BN output columns x a K range (split-K S), 4
 // waves; the product is formed transposed, y^T = W xq^T (W rows are the A operand), so a lane's
@@ -297,8 +251,8 @@ __device__ __forceinline__ int swz(int r) { return (r >> 1) & 7; }
 //    ahead; they are the A operand as loaded and feed all BM / 16 row blocks of the wave.
 //  * xq (L2-resident, shared by every wave) goes global -> registers -> LDS in k128 stages of
 //    128 bytes per row (half the bytes of the 16-bit kernel's stage per k), double buffered.
-//  * split-K is reduced in the launch (f32 slabs + one agent-scope ticket per tile); whoever
-//    stores the tile -- with split-K the last arriver -- applies sx[m] * sw[n].
+//  * split-K: see dgemm.h; whoever stores the tile -- with split-K the last arriver -- applies
+//    sx[m] * sw[n].
 template <typename T, int BM, int BN, bool SC>
 __global__ void __launch_bounds__(NT, 1)
 w8a8_dgemm_kernel(const unsigned char* __restrict__ xq, const float* __restrict__ sx,
@@ -314,18 +268,12 @@ w8a8_dgemm_kernel(const unsigned char* __restrict__ xq, const float* __restrict_
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lr = lane & 15, lg = lane >> 4;
-  // XCD-aware bijective remap (blocks round-robin over 8 XCDs): consecutive virtual ids -- the
-  // S slices of one tile, then the next tile -- land on one XCD
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nb >> 3, r8 = nb & 7;
-  const int v = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int tile = v / S, slice = v - tile * S;
+  const dgemm::TileSlice ts = dgemm::tile_slice(blockIdx.x, gridDim.x, S);
+  const int tile = ts.tile, slice = ts.slice;
   const int n0 = tile * BN;
   const int nvalid = min(BN, N - n0);
-  // k128 tiles of this slice: an even share, the first (kt_total % S) slices one more
-  const int per = kt_total / S, extra = kt_total - per * S;
-  const int kb = slice * per + min(slice, extra);
-  const int nk = per + (slice < extra ? 1 : 0);
+  const dgemm::KSlice ks = dgemm::k_slice(slice, S, kt_total);
+  const int kb = ks.kb, nk = ks.nk;
   const int nrow0 = wid * (BN / 4);
 
   // rows past N / M re-read the last valid row (finite data; those outputs are never stored);
@@ -414,43 +362,8 @@ w8a8_dgemm_kernel(const unsigned char* __restrict__ xq, const float* __restrict_
       }
   }
 
-  if (S > 1) {
-    // slab of this slice: register-major, one 1-KiB wave-instruction per accumulator tile
-    float* slab = ws + ((long long)tile * S + slice) * (NT * NI * MJ * 4);
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < MJ; ++j)
-        *reinterpret_cast<f32x4*>(slab + ((i * MJ + j) * NT + threadIdx.x) * 4) = acc[i][j];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int* flag = reinterpret_cast<int*>(lds + 2 * STAGE_B);
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const int old = __hip_atomic_fetch_add(cnt + tile, 1, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-      const int last = old == S - 1;
-      if (last) __hip_atomic_store(cnt + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *flag = last;
-    }
-    __syncthreads();
-    if (!*flag) return;
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    for (int o = 0; o < S; ++o) {
-      if (o == slice) continue;
-      const float* os = ws + ((long long)tile * S + o) * (NT * NI * MJ * 4);
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int j = 0; j < MJ; ++j)
-          acc[i][j] += *reinterpret_cast<const f32x4*>(os + ((i * MJ + j) * NT + threadIdx.x) * 4);
-    }
-  }
+  LUMEN_DGEMM_SPLITK_REDUCE_OR_RETURN(NT, NI, MJ, acc, ws, cnt, tile, slice, S,
+                                      reinterpret_cast<int*>(lds + 2 * STAGE_B));
 
   // lane holds y^T[n = n0 + nrow0 + 16 i + 4 (lane >> 4) + 0..3][m = 16 j + (lane & 15)]
 #pragma unroll

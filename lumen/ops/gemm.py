@@ -1,9 +1,24 @@
-"""Projection GEMMs for decode: y = x @ W^T.
+"""Projection GEMMs: y = x @ W^T, ``linear_nt`` choosing the route by weight type and M.
 
-At decode batch 1-4 the projection is a pure stream of the weight matrix; for the shapes where it
-measured faster the HIP weight-streaming kernel (``kernels/skinny_gemm.hip``) runs it instead
-of a library GEMM.  Larger batches (and CPU tensors) go to ``torch.matmul`` (hipBLASLt with the
-tuned table)."""
+16-bit weights.  At decode batch 1-4 the projection is a pure stream of the weight matrix; for
+the shapes where it measured faster the HIP weight-streaming kernel (``kernels/skinny_gemm.hip``)
+runs it instead of a library GEMM.  Batches 5..256 take the decode-batch MFMA kernel
+(``kernels/decode_gemm.hip``) where its plan table lists the shape.  Everything else (and CPU
+tensors) goes to ``torch.matmul`` (hipBLASLt with the tuned table), ``mm_nt`` splitting
+training-size outputs at the last whole wave of tiles.
+
+Quantized weights (ops/quant.py), each with a GEMV for M <= 4 and / or a decode MFMA kernel for
+M <= 256 behind a measured plan table, and a fallback that dequantises W into a persistent 16-bit
+scratch and takes the 16-bit path:
+
+* ``QuantWeight``, act None (``fp8``)     -> ``_linear_w8``    kernels/w8_gemm.hip
+* ``QuantWeight``, act "fp8" (``ptpc_fp8``) -> ``_linear_w8a8``  kernels/w8a8_gemm.hip (+ M > 256)
+* ``Mxfp4Weight``, act "fp8" (``mxfp4``)   -> ``_linear_w4a8``  kernels/w4a8_gemm.hip
+* ``Mxfp4Weight``, act None (``mxfp4_a16``) -> ``_linear_w4a16`` kernels/w4a16_gemm.hip
+
+The five decode MFMA kernels share one split-K workspace per (device, stream) (``_dg_splitk_ws``;
+the contract is in ``kernels/dgemm.h``), the plan files one format (``load_plans``) and one place
+(``configs/kernels/``, each with an environment override)."""
 from __future__ import annotations
 
 import os
@@ -55,14 +70,22 @@ def dg_bucket(M: int) -> int:
     return next(b for b in DG_BMS if M <= b)
 
 
+def _y(rows: int, w, like: torch.Tensor, out: Optional[torch.Tensor],
+       dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``out``, or a new [rows, N] result on ``like``'s device, of ``dtype`` (``like``'s where
+    none is given; the act-fp8 routes pass the weight's, their ``like`` being the fp8 xq)."""
+    if out is not None:
+        return out
+    return torch.empty(rows, w.shape[0], device=like.device, dtype=dtype or like.dtype)
+
+
 def decode_gemm(x: torch.Tensor, w: torch.Tensor, bm: int, bn: int, s: int, nw: int = 4,
                 out: Optional[torch.Tensor] = None, flags: int = 0,
                 m: Optional[int] = None) -> torch.Tensor:
     """y = x @ w^T on the decode-batch MFMA kernel with block tile (bm, bn), split-K s and nw
     (4 or 8) waves per block.  ``flags``: bit 0 rotates each tile's k loop start; bit 1 takes
     x in the k-tiled layout [K / 64, bm, 64] (``x_ktiled``) with ``m`` valid rows."""
-    rows = x.shape[0] if not flags & 2 else int(m)
-    y = out if out is not None else torch.empty(rows, w.shape[0], device=x.device, dtype=x.dtype)
+    y = _y(x.shape[0] if not flags & 2 else int(m), w, x, out)
     ws, cnt = _dg_splitk_ws(x.device, w.shape[0], bm, bn, s)
     native().decode_gemm(x, w, y, ws, cnt, bm, bn, s, nw, flags)
     return y
@@ -71,8 +94,8 @@ def decode_gemm(x: torch.Tensor, w: torch.Tensor, bm: int, bn: int, s: int, nw: 
 def _dg_splitk_ws(device, N: int, bm: int, bn: int, s: int) -> tuple:
     """(slab workspace, ticket counters) for a split-K launch of ``s`` slices over [bm, bn]
     tiles of N columns on the current stream; (None, None) for s == 1.  Shared by the 16-bit and
-    the fp8-weight decode GEMM: launches on one stream run one after the other, and every launch
-    leaves the counters zero."""
+    the four quantized decode GEMMs: launches on one stream run one after the other, and every
+    launch leaves the counters zero (kernels/dgemm.h)."""
     if s <= 1:
         return None, None
     # one slab workspace + ticket counters per (device, stream): split-K slabs and tickets
@@ -110,20 +133,39 @@ def dg_workspace(device) -> Optional[tuple]:
     return _dg_ws.get(_dg_key(device))
 
 
+def load_plans(path: str, with_nw: bool = False) -> dict:
+    """{(N, K, BM): (BN, S)} from a plan file ({"plans": [{"N", "K", "BM", "BN", "S"}, ...]});
+    {} for a missing file.  ``with_nw``: (BN, S, waves) -- the 16-bit table's ``NW``, 4 where an
+    entry omits it.  For the W8A8 table a ``BM`` above 256 is an M bucket of the large-M kernel
+    (``W8A8_GEMM_BUCKETS``), whose block tile is fixed."""
+    import json
+
+    plans = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            for e in json.load(f).get("plans", []):
+                nw = (e.get("NW", 4),) if with_nw else ()
+                plans[(e["N"], e["K"], e["BM"])] = (e["BN"], e["S"]) + nw
+    return plans
+
+
+load_w8_plans = load_w8a8_plans = load_w4a8_plans = load_w4a16_plans = load_plans
+
+
+def _plan_path(env: str, name: str) -> str:
+    """The plan file named by the environment variable ``env``, else the shipped table
+    configs/kernels/``name`` (measured wins over the route's fallback only)."""
+    return os.environ.get(env, os.path.join(
+        os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
+        "configs", "kernels", name))
+
+
 def dg_plans() -> dict:
-    """{(N, K, BM): (BN, S, waves)} from configs/kernels/decode_gemm_plans.json (measured wins only)."""
+    """{(N, K, BM): (BN, S, waves)} of the 16-bit decode GEMM."""
     global _dg_plans
     if _dg_plans is None:
-        import json
-
-        path = os.environ.get("LUMEN_DGEMM_PLANS", os.path.join(
-            os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
-            "configs", "kernels", "decode_gemm_plans.json"))
-        _dg_plans = {}
-        if os.path.exists(path):
-            with open(path) as f:
-                for e in json.load(f).get("plans", []):
-                    _dg_plans[(e["N"], e["K"], e["BM"])] = (e["BN"], e["S"], e.get("NW", 4))
+        _dg_plans = load_plans(_plan_path("LUMEN_DGEMM_PLANS", "decode_gemm_plans.json"),
+                               with_nw=True)
     return _dg_plans
 
 
@@ -233,25 +275,11 @@ _w8_old: list = []
 _w8_reserved: dict = {}
 
 
-def load_w8_plans(path: str) -> dict:
-    """{(N, K, BM): (BN, S)} from a plan file in decode_gemm_plans.json's format."""
-    import json
-
-    plans = {}
-    if os.path.exists(path):
-        with open(path) as f:
-            for e in json.load(f).get("plans", []):
-                plans[(e["N"], e["K"], e["BM"])] = (e["BN"], e["S"])
-    return plans
-
-
 def w8_plans() -> dict:
-    """The shipped plan table (measured wins over the dequant + library fallback only)."""
+    """{(N, K, BM): (BN, S)} of the W8A16 decode GEMM."""
     global _w8_plans
     if _w8_plans is None:
-        _w8_plans = load_w8_plans(os.environ.get("LUMEN_W8_PLANS", os.path.join(
-            os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
-            "configs", "kernels", "w8_gemm_plans.json")))
+        _w8_plans = load_plans(_plan_path("LUMEN_W8_PLANS", "w8_gemm_plans.json"))
     return _w8_plans
 
 
@@ -279,8 +307,7 @@ def w8_decode_gemm(x: torch.Tensor, w, bm: int, bn: int, s: int,
                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x @ (w.q * w.scale[:, None])^T on the W8A16 MFMA kernel with block tile (bm, bn) and
     split-K s."""
-    y = out if out is not None else torch.empty(x.shape[0], w.shape[0], device=x.device,
-                                                dtype=x.dtype)
+    y = _y(x.shape[0], w, x, out)
     ws, cnt = _dg_splitk_ws(x.device, w.shape[0], bm, bn, s)
     native().w8_decode_gemm(x, w.q, w.scale, y, ws, cnt, bm, bn, s)
     return y
@@ -293,6 +320,22 @@ def w8_reserve(device, numel: int) -> None:
     _w8_reserved[str(device)] = max(_w8_reserved.get(str(device), 0), int(numel))
 
 
+def _scratch16(w) -> torch.Tensor:
+    """The [N, K] view for ``w`` of the persistent 16-bit scratch of the current (device, stream)
+    and ``w.dtype``, grown where needed (never below ``w8_reserve``'s floor)."""
+    N, K = w.shape
+    key = _dg_key(w.device) + (w.dtype,)
+    buf = _w8_scratch.get(key)
+    if buf is None or buf.numel() < N * K:
+        # a superseded scratch stays alive (_w8_old): a captured graph keeps pointing at it
+        if buf is not None:
+            _w8_old.append(buf)
+        buf = torch.empty(max(N * K, _w8_reserved.get(str(w.device), 0)), dtype=w.dtype,
+                          device=w.device)
+        _w8_scratch[key] = buf
+    return buf[:N * K].view(N, K)
+
+
 def w8_dequant(w, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The 16-bit weight of ``w`` (bit-identical to ``w.dequant()``), by default in the
     persistent scratch of the current (device, stream): valid until the next call there."""
@@ -300,16 +343,7 @@ def w8_dequant(w, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     if K % 16:
         raise ValueError(f"fp8 weights on the GPU need K % 16 == 0, got K = {K}")
     if out is None:
-        key = _dg_key(w.device) + (w.dtype,)
-        buf = _w8_scratch.get(key)
-        if buf is None or buf.numel() < N * K:
-            # a superseded scratch stays alive (_w8_old): a captured graph keeps pointing at it
-            if buf is not None:
-                _w8_old.append(buf)
-            buf = torch.empty(max(N * K, _w8_reserved.get(str(w.device), 0)), dtype=w.dtype,
-                              device=w.device)
-            _w8_scratch[key] = buf
-        out = buf[:N * K].view(N, K)
+        out = _scratch16(w)
     native().w8_dequant(w.q, w.scale, out)
     return out
 
@@ -334,27 +368,11 @@ W8A8_GEMM_BUCKETS = (512, 2048, 4096)   # M buckets of the large-M plans (the la
 _w8a8_plans: Optional[dict] = None
 
 
-def load_w8a8_plans(path: str) -> dict:
-    """{(N, K, bucket): (BN, S)} from a plan file in w8_gemm_plans.json's format.  ``BM`` <= 256
-    is a decode-kernel bucket (and its block height); a larger ``BM`` is an M bucket of the
-    large-M kernel (``W8A8_GEMM_BUCKETS``), whose block tile is fixed."""
-    import json
-
-    plans = {}
-    if os.path.exists(path):
-        with open(path) as f:
-            for e in json.load(f).get("plans", []):
-                plans[(e["N"], e["K"], e["BM"])] = (e["BN"], e["S"])
-    return plans
-
-
 def w8a8_plans() -> dict:
-    """The shipped plan table (measured wins over the fake-quant fallback only)."""
+    """{(N, K, BM): (BN, S)} of the W8A8 kernels (BM above 256: a large-M kernel bucket)."""
     global _w8a8_plans
     if _w8a8_plans is None:
-        _w8a8_plans = load_w8a8_plans(os.environ.get("LUMEN_W8A8_PLANS", os.path.join(
-            os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
-            "configs", "kernels", "w8a8_gemm_plans.json")))
+        _w8a8_plans = load_plans(_plan_path("LUMEN_W8A8_PLANS", "w8a8_gemm_plans.json"))
     return _w8a8_plans
 
 
@@ -387,8 +405,7 @@ def act_quant_fp8(x: torch.Tensor) -> tuple:
 
 
 def w8a8_gemv(xq: torch.Tensor, sx: torch.Tensor, w, out: Optional[torch.Tensor] = None):
-    y = out if out is not None else torch.empty(xq.shape[0], w.shape[0], device=xq.device,
-                                                dtype=w.dtype)
+    y = _y(xq.shape[0], w, xq, out, w.dtype)
     native().w8a8_gemv(xq, sx, w.q, w.scale, y)
     return y
 
@@ -397,8 +414,7 @@ def w8a8_decode_gemm(xq: torch.Tensor, sx: torch.Tensor, w, bm: int, bn: int, s:
                      form: Optional[int] = None, out: Optional[torch.Tensor] = None):
     """y = (xq @ w.q^T) * sx[:, None] * w.scale[None, :] on the W8A8 decode MFMA kernel with block
     tile (bm, bn), split-K s and MFMA form (``W8A8_FORMS``)."""
-    y = out if out is not None else torch.empty(xq.shape[0], w.shape[0], device=xq.device,
-                                                dtype=w.dtype)
+    y = _y(xq.shape[0], w, xq, out, w.dtype)
     ws, cnt = _dg_splitk_ws(xq.device, w.shape[0], bm, bn, s)
     native().w8a8_decode_gemm(xq, sx, w.q, w.scale, y, ws, cnt, bm, bn, s,
                               W8A8_FORM if form is None else form)
@@ -407,18 +423,38 @@ def w8a8_decode_gemm(xq: torch.Tensor, sx: torch.Tensor, w, bm: int, bn: int, s:
 
 def w8a8_gemm(xq: torch.Tensor, sx: torch.Tensor, w, out: Optional[torch.Tensor] = None):
     """The same product on the block-tiled large-M kernel (M > 256)."""
-    y = out if out is not None else torch.empty(xq.shape[0], w.shape[0], device=xq.device,
-                                                dtype=w.dtype)
+    y = _y(xq.shape[0], w, xq, out, w.dtype)
     native().w8a8_gemm(xq, sx, w.q, w.scale, y)
     return y
+
+
+def _act_fp8_fallback(xq: torch.Tensor, sx: torch.Tensor, w, w16: torch.Tensor) -> torch.Tensor:
+    """The 16-bit path on xq widened (exact) and the dequantised weight ``w16``, rows times sx."""
+    y = linear_nt(xq.to(w.dtype), w16)
+    return (y.float() * sx[:, None]).to(w.dtype)
 
 
 def w8a8_fallback(xq: torch.Tensor, sx: torch.Tensor, w) -> torch.Tensor:
     """Fake-quant: every e4m3 value is exact in bf16 / fp16, so the 16-bit path on (xq widened,
     W dequantised) followed by the per-row sx computes the same function to within one extra
     16-bit rounding of W * sw (and of the unscaled product)."""
-    y = linear_nt(xq.to(w.dtype), w8_dequant(w))
-    return (y.float() * sx[:, None]).to(w.dtype)
+    return _act_fp8_fallback(xq, sx, w, w8_dequant(w))
+
+
+def _quant_dtype(x: torch.Tensor, w, word: str) -> None:
+    """Raises where the activations are not of the model dtype the weight was quantized from
+    (``word``: fp8 / mxfp4, for the message)."""
+    if x.dtype != w.dtype:
+        raise ValueError(f"{word} weight of a {w.dtype} model applied to {x.dtype} activations")
+
+
+def _quant_args(x: torch.Tensor, w, word: str) -> Optional[torch.Tensor]:
+    """The argument check of the quantized GPU routes: raises on a dtype or shape mismatch; the
+    empty result for M == 0, else None."""
+    _quant_dtype(x, w, word)
+    if x.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"activations {tuple(x.shape)} do not match the weight {tuple(w.shape)}")
+    return x.new_empty(0, w.shape[0]) if x.shape[0] == 0 else None
 
 
 def _linear_w8a8(x: torch.Tensor, w) -> torch.Tensor:
@@ -427,13 +463,9 @@ def _linear_w8a8(x: torch.Tensor, w) -> torch.Tensor:
 
         xq, sx = quantize_fp8_tokens(x)
         return ((xq.float() @ w.q.float().t()) * sx[:, None] * w.scale[None, :]).to(x.dtype)
-    if x.dtype != w.dtype:
-        raise ValueError(f"fp8 weight of a {w.dtype} model applied to {x.dtype} activations")
-    if x.dim() != 2 or x.shape[1] != w.shape[1]:
-        raise ValueError(f"activations {tuple(x.shape)} do not match the weight {tuple(w.shape)}")
+    if (empty := _quant_args(x, w, "fp8")) is not None:
+        return empty
     M = x.shape[0]
-    if M == 0:
-        return x.new_empty(0, w.shape[0])
     xq, sx = act_quant_fp8(x)
     if W8:
         if M <= 4 and w.shape[0] % 4 == 0:
@@ -456,18 +488,11 @@ W4A8_BNS = {16: (64, 128), 64: (64, 128), 128: (64, 128), 256: (64,)}   # compil
 _w4a8_plans: Optional[dict] = None
 
 
-def load_w4a8_plans(path: str) -> dict:
-    """{(N, K, BM): (BN, S)} from a plan file in w8_gemm_plans.json's format."""
-    return load_w8_plans(path)
-
-
 def w4a8_plans() -> dict:
-    """The shipped plan table (measured wins over the fallback only)."""
+    """{(N, K, BM): (BN, S)} of the W4A8 decode GEMM."""
     global _w4a8_plans
     if _w4a8_plans is None:
-        _w4a8_plans = load_w4a8_plans(os.environ.get("LUMEN_W4A8_PLANS", os.path.join(
-            os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
-            "configs", "kernels", "w4a8_gemm_plans.json")))
+        _w4a8_plans = load_plans(_plan_path("LUMEN_W4A8_PLANS", "w4a8_gemm_plans.json"))
     return _w4a8_plans
 
 
@@ -494,8 +519,7 @@ def w4a8_decode_gemm(xq: torch.Tensor, sx: torch.Tensor, w, bm: int, bn: int, s:
                      out: Optional[torch.Tensor] = None):
     """y = (xq @ wdq^T) * sx[:, None] on the W4A8 decode MFMA kernel with block tile (bm, bn) and
     split-K s."""
-    y = out if out is not None else torch.empty(xq.shape[0], w.shape[0], device=xq.device,
-                                                dtype=w.dtype)
+    y = _y(xq.shape[0], w, xq, out, w.dtype)
     ws, cnt = _dg_splitk_ws(xq.device, w.shape[0], bm, bn, s)
     native().w4a8_decode_gemm(xq, sx, w.q, w.scale, y, ws, cnt, bm, bn, s)
     return y
@@ -508,16 +532,7 @@ def w4_dequant(w, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     if K % 16:
         raise ValueError(f"mxfp4 weights on the GPU need K % 16 == 0, got K = {K}")
     if out is None:
-        key = _dg_key(w.device) + (w.dtype,)
-        buf = _w8_scratch.get(key)
-        if buf is None or buf.numel() < N * K:
-            # a superseded scratch stays alive (_w8_old): a captured graph keeps pointing at it
-            if buf is not None:
-                _w8_old.append(buf)
-            buf = torch.empty(max(N * K, _w8_reserved.get(str(w.device), 0)), dtype=w.dtype,
-                              device=w.device)
-            _w8_scratch[key] = buf
-        out = buf[:N * K].view(N, K)
+        out = _scratch16(w)
     native().w4_dequant(w.q, w.scale, out)
     return out
 
@@ -526,8 +541,7 @@ def w4a8_fallback(xq: torch.Tensor, sx: torch.Tensor, w) -> torch.Tensor:
     """Every e4m3 value is exact in bf16 / fp16, so the 16-bit path on (xq widened, W
     dequantised) followed by the per-row sx computes the same function to within one extra 16-bit
     rounding of the unscaled product (and, in fp16, of a weight outside its range)."""
-    y = linear_nt(xq.to(w.dtype), w4_dequant(w))
-    return (y.float() * sx[:, None]).to(w.dtype)
+    return _act_fp8_fallback(xq, sx, w, w4_dequant(w))
 
 
 def _linear_w4a8(x: torch.Tensor, w) -> torch.Tensor:
@@ -536,13 +550,9 @@ def _linear_w4a8(x: torch.Tensor, w) -> torch.Tensor:
 
         xq, sx = quantize_fp8_tokens(x)
         return ((xq.float() @ w.dequant_f32().t()) * sx[:, None]).to(x.dtype)
-    if x.dtype != w.dtype:
-        raise ValueError(f"mxfp4 weight of a {w.dtype} model applied to {x.dtype} activations")
-    if x.dim() != 2 or x.shape[1] != w.shape[1]:
-        raise ValueError(f"activations {tuple(x.shape)} do not match the weight {tuple(w.shape)}")
+    if (empty := _quant_args(x, w, "mxfp4")) is not None:
+        return empty
     M = x.shape[0]
-    if M == 0:
-        return x.new_empty(0, w.shape[0])
     xq, sx = act_quant_fp8(x)
     p = w4a8_plan(M, w) if W8 else None
     if p is not None:
@@ -562,18 +572,11 @@ W4A16_GEMV_CFGS = (41, 42, 81, 82)   # 10 R + GS: compiled (rows per wave group,
 _w4a16_plans: Optional[dict] = None
 
 
-def load_w4a16_plans(path: str) -> dict:
-    """{(N, K, BM): (BN, S)} from a plan file in w8_gemm_plans.json's format."""
-    return load_w8_plans(path)
-
-
 def w4a16_plans() -> dict:
-    """The shipped plan table (measured wins over the fallback only)."""
+    """{(N, K, BM): (BN, S)} of the W4A16 decode GEMM."""
     global _w4a16_plans
     if _w4a16_plans is None:
-        _w4a16_plans = load_w4a16_plans(os.environ.get("LUMEN_W4A16_PLANS", os.path.join(
-            os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
-            "configs", "kernels", "w4a16_gemm_plans.json")))
+        _w4a16_plans = load_plans(_plan_path("LUMEN_W4A16_PLANS", "w4a16_gemm_plans.json"))
     return _w4a16_plans
 
 
@@ -593,8 +596,7 @@ def w4a16_plan(x: torch.Tensor, w) -> Optional[tuple]:
 def w4a16_gemv(x: torch.Tensor, w, out: Optional[torch.Tensor] = None, cfg: int = 0):
     """y = x @ w.dequant()^T for 1 <= M <= 4 on the 4-bit GEMV (``cfg``: one of
     ``W4A16_GEMV_CFGS`` instead of the measured default)."""
-    y = out if out is not None else torch.empty(x.shape[0], w.shape[0], device=x.device,
-                                                dtype=x.dtype)
+    y = _y(x.shape[0], w, x, out)
     native().w4a16_gemv(x, w.q, w.scale, y, cfg)
     return y
 
@@ -602,8 +604,7 @@ def w4a16_gemv(x: torch.Tensor, w, out: Optional[torch.Tensor] = None, cfg: int 
 def w4a16_decode_gemm(x: torch.Tensor, w, bm: int, bn: int, s: int,
                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x @ w.dequant()^T on the W4A16 MFMA kernel with block tile (bm, bn) and split-K s."""
-    y = out if out is not None else torch.empty(x.shape[0], w.shape[0], device=x.device,
-                                                dtype=x.dtype)
+    y = _y(x.shape[0], w, x, out)
     ws, cnt = _dg_splitk_ws(x.device, w.shape[0], bm, bn, s)
     native().w4a16_decode_gemm(x, w.q, w.scale, y, ws, cnt, bm, bn, s)
     return y
@@ -618,12 +619,8 @@ def w4a16_fallback(x: torch.Tensor, w) -> torch.Tensor:
 def _linear_w4a16(x: torch.Tensor, w) -> torch.Tensor:
     if not use_native(x):
         return (x.float() @ w.dequant().float().t()).to(x.dtype)
-    if x.dtype != w.dtype:
-        raise ValueError(f"mxfp4 weight of a {w.dtype} model applied to {x.dtype} activations")
-    if x.dim() != 2 or x.shape[1] != w.shape[1]:
-        raise ValueError(f"activations {tuple(x.shape)} do not match the weight {tuple(w.shape)}")
-    if x.shape[0] == 0:
-        return x.new_empty(0, w.shape[0])
+    if (empty := _quant_args(x, w, "mxfp4")) is not None:
+        return empty
     if W8 and w4a16_gemv_ok(x, w):
         return w4a16_gemv(x, w)
     p = w4a16_plan(x, w) if W8 else None
@@ -639,8 +636,8 @@ def _linear_w8(x: torch.Tensor, w) -> torch.Tensor:
         raise ValueError(f"QuantWeight.act must be None or 'fp8', got {w.act}")
     if not use_native(x):
         return x @ w.dequant().to(x.dtype).t()
-    if x.dtype != w.dtype:
-        raise ValueError(f"fp8 weight of a {w.dtype} model applied to {x.dtype} activations")
+    # (dtype only: this route's fallback takes whatever torch.matmul takes, as it always has)
+    _quant_dtype(x, w, "fp8")
     # the GEMV at every M <= 4: the fastest of the fp8 routes there.  Known loss against 16-bit
     # weights: at M = 3..4 on the wide projections it is slower than the 16-bit GEMV (M = 4:
     # qkv 29.5 vs 25.5 us, gate|up 48.0 vs 38.7 us, profiles/w8_serve)

@@ -5,8 +5,11 @@ weight holders.
 
 A projection weight ``w [N, K]`` is stored as OCP e4m3fn (``torch.float8_e4m3fn``, gfx950's fp8)
 with one f32 scale per output row; activations, accumulation and outputs keep their types.  The
-kernels that consume it are in ``kernels/w8_gemm.hip``, the dispatch in ``ops/gemm.py``.  The
-weight quantizer runs once per projection at load time in plain torch: it is not a hot path.
+kernels that consume it are in ``kernels/w8_gemm.hip``, the dispatch in ``ops/gemm.py``.  (The
+decode MFMA kernels of all four modes take their tile / k-slice map and their in-launch split-K
+reduction from ``kernels/dgemm.h``, the GEMVs their dot product and row sum from
+``kernels/gemv.h``.)  The weight quantizer runs once per projection at load time in plain torch:
+it is not a hot path.
 Under ``ptpc_fp8`` (``QuantWeight.act == "fp8"``) the activations are quantized per token row at
 run time: ``quantize_fp8_tokens`` is the definition and the CPU path, kernels/w8a8_gemm.hip's
 ``act_quant_fp8`` the GPU path."""

@@ -932,6 +932,63 @@ def test_decode_gemm_variants(bm):
                         assert rel(y, ref) < 1e-2, (fl, bn, nw, s, M, rel(y, ref))
 
 
+def test_splitk_families_share_workspace():
+    """The five decode GEMMs (kernels/dgemm.h's split-K reduction) take turns on ONE stream's slab
+    workspace and ticket counters: 16-bit, W8A16, W8A8, W4A8 (BM = 64 and 16) and W4A16 in this
+    order and in reverse, split-K 2 and 3, a ragged last column tile.  After every launch the
+    counters are zero and the result meets its family's own bound."""
+    import lumen.ops.gemm as gm
+    from tests import test_mxfp4_gpu as t48, test_w4a16_gpu as t416, test_w8_gpu as t8
+    from tests import test_w8a8_gpu as t88
+
+    g = torch.Generator(device="cpu").manual_seed(11)
+    K, M, dt, dev = 640, 5, torch.bfloat16, torch.device("cuda", 0)
+    n_of = lambda bn: 3 * bn + 12
+
+    def dg16():
+        bn = gm.DG_BNS[64][0]
+        w = (torch.randn(n_of(bn), K, generator=g) * 0.05).to(dev, dt)
+        x = torch.randn(M, K, generator=g).to(dev, dt)
+        ref = x.float() @ w.float().t()
+
+        def run(s):
+            y = gm.decode_gemm(x, w, 64, bn, s)
+            assert y.shape == ref.shape and rel(y, ref) < 1e-2, ("16-bit", s, rel(y, ref))
+        return run
+
+    def w8():
+        bn = gm.W8_BNS[64][0]
+        qw = t8.rand_qw(n_of(bn), K, dt, g)
+        x = torch.randn(M, K, generator=g).to(dev, dt)
+        return lambda s: t8.check(gm.w8_decode_gemm(x, qw, 64, bn, s), x, qw, ("w8", s))
+
+    def w8a8():
+        bn = gm.W8A8_BNS[64][0]
+        xq, sx, w = t88.rand_case(M, n_of(bn), K, dt, g)
+        return lambda s: t88.check(gm.w8a8_decode_gemm(xq, sx, w, 64, bn, s), xq, sx, w,
+                                   ("w8a8", s))
+
+    def w4a8(bm):
+        bn = gm.W4A8_BNS[bm][0]
+        xq, sx, w = t48.rand_case(M, n_of(bn), K, dt, g)
+        return lambda s: t48.check(gm.w4a8_decode_gemm(xq, sx, w, bm, bn, s), xq, sx, w,
+                                   ("w4a8", bm, s))
+
+    def w4a16():
+        bn = gm.W4A16_BNS[64][0]
+        x, w = t416.rand_case(M, n_of(bn), K, dt, g)
+        return lambda s: t416.check(gm.w4a16_decode_gemm(x, w, 64, bn, s), x, w, ("w4a16", s))
+
+    runs = [dg16(), w8(), w8a8(), w4a8(64), w4a8(16), w4a16()]
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    for order in (runs, runs[::-1]):
+        for s in (2, 3):
+            for run in order:
+                run(s)
+                assert torch.cuda.current_stream(dev).cuda_stream == stream
+                assert int(gm.dg_workspace(dev)[1].abs().sum()) == 0
+
+
 @pytest.mark.parametrize("N,K", [(12288, 4096), (4096, 4096), (22016, 4096), (4096, 11008),
                                  (32000, 4096)])
 @pytest.mark.parametrize("M", [64, 100, 200, 256])

@@ -438,6 +438,43 @@ def test_decode_gemm_plan_table_loads():
         assert k % 64 == 0 and bm in gemm.DG_BMS and nw in (4, 8) and 1 <= s <= k // 64
 
 
+def test_plan_getters_share_one_reader(tmp_path, monkeypatch):
+    """The five ``*_plans()`` getters honour their environment override and give {} for a missing
+    file; ``dg_plans()`` fills in 4 waves where an entry has no ``NW``; the ``load_*_plans`` names
+    parse one file to one dictionary."""
+    import json
+
+    from lumen.ops import gemm
+
+    path = tmp_path / "plans.json"
+    path.write_text(json.dumps({"plans": [{"N": 4096, "K": 4096, "BM": 64, "BN": 128, "S": 2},
+                                          {"N": 512, "K": 256, "BM": 256, "BN": 64, "S": 1,
+                                           "NW": 8}]}))
+    want = {(4096, 4096, 64): (128, 2), (512, 256, 256): (64, 1)}
+    loaders = (gemm.load_w8_plans, gemm.load_w8a8_plans, gemm.load_w4a8_plans,
+               gemm.load_w4a16_plans)
+    for load in loaders:
+        assert load(str(path)) == want
+        assert load(str(tmp_path / "missing.json")) == {}
+    getters = {"LUMEN_DGEMM_PLANS": ("_dg_plans", gemm.dg_plans),
+               "LUMEN_W8_PLANS": ("_w8_plans", gemm.w8_plans),
+               "LUMEN_W8A8_PLANS": ("_w8a8_plans", gemm.w8a8_plans),
+               "LUMEN_W4A8_PLANS": ("_w4a8_plans", gemm.w4a8_plans),
+               "LUMEN_W4A16_PLANS": ("_w4a16_plans", gemm.w4a16_plans)}
+    for env, (cache, get) in getters.items():
+        monkeypatch.setenv(env, str(path))
+        monkeypatch.setattr(gemm, cache, None)
+        if get is gemm.dg_plans:
+            assert get() == {(4096, 4096, 64): (128, 2, 4), (512, 256, 256): (64, 1, 8)}
+        else:
+            assert get() == want, env
+        assert getattr(gemm, cache) is get()          # cached in the getter's own global
+        monkeypatch.setenv(env, str(tmp_path / "missing.json"))
+        monkeypatch.setattr(gemm, cache, None)
+        assert get() == {}, env
+        monkeypatch.setattr(gemm, cache, None)        # the next user reloads the shipped table
+
+
 @pytest.mark.parametrize("deadline", [300.0, 0.01])
 def test_bench_tp_serving_section_and_deadline(deadline):
     """bench.py's TP = N serving section (forced on gloo with --serve_tp 2, tiny model, 8
