@@ -14,7 +14,8 @@ Reference quirks fixed: zero1's default config path points at confi
 JSON decides precision (2), every variant writes the metrics row (3), imports work from any cwd
 (4), world size comes from the launcher (6), resume resolves on every rank (7), tokens/s is
 recorded (8), the visible-device set is validated (12), a CPU/gloo path exists (13).
-lumen extras: --synthetic, --max_steps, --max_length, --init, --device, --no_gradient_checkpointing.
+lumen extras: --synthetic, --max_steps, --max_length, --init, --device, --no_gradient_checkpointing,
+--base_quantization.
 """
 from __future__ import annotations
 
@@ -101,6 +102,10 @@ def build_parser(variant: str) -> argparse.ArgumentParser:
                     help="same as --gradient_checkpointing false")
     ap.add_argument("--no_fuse_accumulation", action="store_true",
                     help="run every accumulation micro-batch as its own forward / backward")
+    ap.add_argument("--base_quantization", default="none", choices=["none", "fp8", "mxfp4"],
+                    help="store the frozen decoder projections once, quantized (per-row e4m3fn or "
+                         "OCP MXFP4, round to nearest: the quantizers of serving's --quantization "
+                         "fp8 / mxfp4_a16) and dequantise them per use; ZeRO stage 0 / 1 / 2")
     ap.add_argument("--metrics_csv", default="results/training_metrics.csv")
     return ap
 
@@ -162,7 +167,8 @@ def main(variant: str, argv=None) -> dict:
         synthetic_samples=args.synthetic_samples, init=args.init, experiment=experiment,
         synthetic_min_len=args.synthetic_min_len, pack_sequences=not args.no_packing,
         prefetch=args.prefetch, pack_tokens=args.pack_tokens,
-        fuse_accumulation=not args.no_fuse_accumulation)
+        fuse_accumulation=not args.no_fuse_accumulation,
+        base_quantization=args.base_quantization)
     t0 = time.time()
     trainer = Trainer(targs, ds, env)
     result = trainer.train()

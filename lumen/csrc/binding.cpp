@@ -91,6 +91,10 @@ hipError_t lumen_w4a8_decode_gemm(int, const void*, const float*, const void*, c
                                   hipStream_t);
 hipError_t lumen_w4_dequant(int, const void*, const void*, void*, long long, long long,
                             hipStream_t);
+hipError_t lumen_qbase_dequant(int, int, const void*, const void*, void*, long long, long long,
+                               long long, hipStream_t);
+hipError_t lumen_qbase_dequant_t(int, int, const void*, const void*, void*, long long, long long,
+                                 hipStream_t);
 hipError_t lumen_w4a16_gemv(int, const void*, const void*, const void*, void*, int, int, int,
                             long long, long long, int, hipStream_t);
 hipError_t lumen_w4a16_decode_gemm(int, const void*, const void*, const void*, void*, float*, int*,
@@ -554,6 +558,64 @@ void w4_dequant(const at::Tensor& q, const at::Tensor& scale, at::Tensor& out) {
   check(lumen_w4_dequant(dcode(out), q.data_ptr(), scale.data_ptr(), out.data_ptr(), q.size(0),
                          out.size(1), cur_stream()),
         "w4_dequant");
+}
+
+// Quantized frozen base for training (kernels/qbase.hip).  q / scale: an ops.quant QuantWeight's
+// (e4m3fn [N, K], f32 [N]) or Mxfp4Weight's (uint8 codes and E8M0 block scales); K is the output's.
+// Every refusal is an std::invalid_argument raised before any launch.
+int need_qbase(const at::Tensor& q, const at::Tensor& scale, const at::Tensor& out, int64_t N,
+               int64_t K, const char* what) {
+  const std::string pre = std::string("lumen: ") + what + ": invalid argument: ";
+  if (!out.is_cuda() || out.dim() != 2 ||
+      (out.scalar_type() != at::kBFloat16 && out.scalar_type() != at::kHalf))
+    throw std::invalid_argument(pre + "the output must be a 2-D 16-bit GPU tensor");
+  if (!q.is_cuda() || !scale.is_cuda() || q.device() != out.device() ||
+      scale.device() != out.device())
+    throw std::invalid_argument(pre + "codes, scales and output must be on one GPU");
+  if (K < 16 || K % 16 != 0 || N < 8 || N % 8 != 0)
+    throw std::invalid_argument(pre + "needs K % 16 == 0 and N % 8 == 0");
+  int fmt;
+  if (q.scalar_type() == at::kFloat8_e4m3fn) {
+    need_w8(q, scale, what);
+    if (q.size(0) != N || q.size(1) != K)
+      throw std::invalid_argument(pre + "output shape does not match the codes");
+    fmt = 0;
+  } else {
+    need_w4(q, scale, K, what);
+    if (q.size(0) != N) throw std::invalid_argument(pre + "output shape does not match the codes");
+    fmt = 1;
+  }
+  if (((reinterpret_cast<uintptr_t>(q.data_ptr()) | reinterpret_cast<uintptr_t>(out.data_ptr())) &
+       15) != 0)
+    throw std::invalid_argument(pre + "codes and output must be 16-byte aligned");
+  return fmt;
+}
+
+// out [N, K] (rows at stride ld >= K, ld % 8 == 0; columns K..ld are not written) = dequant()
+void qbase_dequant(const at::Tensor& q, const at::Tensor& scale, at::Tensor& out, int64_t ld) {
+  const char* what = "qbase_dequant";
+  const int64_t N = out.dim() == 2 ? out.size(0) : 0, K = out.dim() == 2 ? out.size(1) : 0;
+  const int fmt = need_qbase(q, scale, out, N, K, what);
+  if (ld < K || ld % 8 != 0 || out.stride(1) != 1 || out.stride(0) != ld)
+    throw std::invalid_argument("lumen: qbase_dequant: invalid argument: the output must be an "
+                                "[N, K] view with unit column stride and row stride ld >= K, "
+                                "ld % 8 == 0");
+  check(lumen_qbase_dequant(fmt, dcode(out), q.data_ptr(), scale.data_ptr(), out.data_ptr(), N, K,
+                            ld, cur_stream()),
+        what);
+}
+
+// out [K, N] (contiguous) = dequant().t()
+void qbase_dequant_t(const at::Tensor& q, const at::Tensor& scale, at::Tensor& out) {
+  const char* what = "qbase_dequant_t";
+  const int64_t K = out.dim() == 2 ? out.size(0) : 0, N = out.dim() == 2 ? out.size(1) : 0;
+  const int fmt = need_qbase(q, scale, out, N, K, what);
+  if (!out.is_contiguous())
+    throw std::invalid_argument("lumen: qbase_dequant_t: invalid argument: the output must be a "
+                                "contiguous [K, N] tensor");
+  check(lumen_qbase_dequant_t(fmt, dcode(out), q.data_ptr(), scale.data_ptr(), out.data_ptr(), N,
+                              K, cur_stream()),
+        what);
 }
 
 // MXFP4 weight-only projections (kernels/w4a16_gemm.hip): x / y 16-bit, q / scale as above
@@ -1411,6 +1473,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("w8a8_gemm", &w8a8_gemm);
   m.def("w4a8_decode_gemm", &w4a8_decode_gemm);
   m.def("w4_dequant", &w4_dequant);
+  m.def("qbase_dequant", &qbase_dequant);
+  m.def("qbase_dequant_t", &qbase_dequant_t);
   m.def("w4a16_gemv", &w4a16_gemv);
   m.def("w4a16_decode_gemm", &w4a16_decode_gemm);
   m.def("mlp_gemm", &mlp_gemm, py::arg("epi"), py::arg("x"), py::arg("w"), py::arg("c"),

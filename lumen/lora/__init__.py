@@ -17,7 +17,9 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from ..models.layers import Linear
+from ..models.layers import Linear, base_quantization_of
+
+BASE_QUANT_KEY = "lumen_base_quantization"
 
 DEFAULT_TARGETS = ["q_proj", "k_proj", "v_proj", "o_proj"]
 _OPT_ALIASES = {"o_proj": "out_proj"}
@@ -121,9 +123,19 @@ def save_adapter(model: nn.Module, path: str, base_model_name: str = "",
         "r": cfg.r, "rank_pattern": {}, "revision": None,
         "target_modules": sorted(set(cfg.target_modules)), "task_type": cfg.task_type,
         "use_dora": False, "use_rslora": False,
+        # lumen-specific (PEFT ignores unknown keys): how the frozen base the adapter was trained
+        # over was stored (--base_quantization).  Evaluate and serve it over the same base.
+        BASE_QUANT_KEY: base_quantization_of(model),
     }
     with open(os.path.join(path, "adapter_config.json"), "w") as f:
         json.dump(conf, f, indent=2)
+
+
+def read_base_quantization(path: str) -> str:
+    """The ``--base_quantization`` an adapter directory was trained under ("none" where the
+    adapter predates the key)."""
+    with open(os.path.join(path, "adapter_config.json")) as f:
+        return json.load(f).get(BASE_QUANT_KEY) or "none"
 
 
 def read_adapter_config(path: str) -> LoraConfig:

@@ -18,6 +18,10 @@ from ..ops import lora as lora_ops
 from ..ops.lora import lora_linear, linear
 from ..ops.transpose import transpose_2d
 from ..ops.norm import rms_norm
+from ..ops.gemm import dequant_into, qbase_check_shape
+from ..ops.quant import quantize_fp8_rows, quantize_mxfp4_rows
+
+BASE_QUANT_KINDS = ("fp8", "mxfp4")
 
 
 class LoRAAdapter(nn.Module):
@@ -81,8 +85,13 @@ class Linear(nn.Module):
         self._wext: Optional[torch.Tensor] = None  # [W | s B_bd | 0] (LoRA fold), see fold_weight
         self._wext_key = None
         self._tail_key = None
+        # --base_quantization: the weight-only holder (ops/quant.py) that replaces ``weight``'s
+        # 16-bit storage, see quantize_base
+        self.qweight = None
 
     def weight_fn(self) -> torch.Tensor:
+        if self.qweight is not None:
+            return dequant_into(self.qweight, "nk")
         return self.weight
 
     def weight_t_fn(self) -> Optional[torch.Tensor]:
@@ -96,6 +105,9 @@ class Linear(nn.Module):
         W = self.weight
         if not self.transpose_bwd or W.requires_grad:
             return None
+        if self.qweight is not None:
+            # W^T straight from the quantized storage: nothing resident, nothing cached
+            return dequant_into(self.qweight, "kn")
         if getattr(W, "_lumen_gathered", False):
             wt = getattr(W, "_lumen_wt", None)  # transposed by the ZeRO-3 coordinator off-path
             if wt is not None:
@@ -118,6 +130,12 @@ class Linear(nn.Module):
         ``static``: eligibility of the layer itself (the ZeRO-3 layout asks before the weight
         is partitioned); otherwise also of the weight as currently bound."""
         lo, W = self.lora, self.weight
+        # A quantized base does not fold, in the static query as in the other (where the emptied
+        # weight already answers 0): the fold needs a resident [W | s B_bd | 0] in 16 bits, which
+        # is what --base_quantization removes.  The adapter takes the un-folded v3 path; the
+        # ~1.3 ms/step the fold measured on Llama-2-7B (README) is given up here.
+        if self.qweight is not None:
+            return 0
         if (not lora_ops.FOLD or lo is None or not self.lora_enabled or W.requires_grad
                 or not W.is_cuda or W.dtype not in (torch.bfloat16, torch.float16)
                 or not lora_ops.use_native(W)):
@@ -214,6 +232,51 @@ class Linear(nn.Module):
                                 device=self.weight.device)
         return self.lora
 
+    # ---- quantized frozen base (--base_quantization) --------------------------------------------
+    @torch.no_grad()
+    def quantize_base(self, kind: str, name: Optional[str] = None):
+        """Store the frozen weight once, as weight-only fp8 (per-row e4m3fn) or MXFP4 -- the
+        quantizers serving uses -- and free its 16-bit storage.  ``weight`` stays the same
+        ``nn.Parameter`` with empty data and its logical shape in ``_zero_shape`` (as ZeRO-3's
+        placeholders, so ``count_parameters`` still reports the full model); ``weight_fn`` /
+        ``weight_t_fn`` dequantise per use into the training scratch of projection ``name``
+        (ops/gemm.py ``dequant_into``).  Returns the holder."""
+        if kind not in BASE_QUANT_KINDS:
+            raise ValueError(f"base quantization must be one of {BASE_QUANT_KINDS}, got {kind!r}")
+        if self.qweight is not None:
+            raise RuntimeError("this linear's base is already quantized")
+        W = self.weight
+        if W.requires_grad:
+            raise RuntimeError("only a frozen weight can be quantized (--base_quantization "
+                               "trains adapters over a fixed base)")
+        if W.dim() != 2 or W.numel() == 0 or getattr(W, "_lumen_gathered", False):
+            raise RuntimeError("quantize_base needs the whole 16-bit weight (before ZeRO-3 "
+                               "partitions it)")
+        qbase_check_shape(*W.shape)
+        if W.is_cuda and W.dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"a quantized base on the GPU needs a 16-bit model dtype, got {W.dtype}")
+        w = quantize_fp8_rows(W) if kind == "fp8" else quantize_mxfp4_rows(W)
+        w.act = None
+        w.name = name or self.seg_names[0]
+        shape = tuple(W.shape)
+        self.invalidate_weight_cache()
+        W.data = torch.empty(0, dtype=W.dtype, device=W.device)
+        W._zero_shape = shape
+        self.qweight = w
+        self.base_quantization = kind
+        return w
+
+    @torch.no_grad()
+    def dequantize_base(self) -> None:
+        """Back to 16-bit storage holding ``dequant()``: the same base function, mergeable."""
+        if self.qweight is None:
+            return
+        self.weight.data = self.qweight.dequant().contiguous()
+        del self.weight._zero_shape
+        self.qweight = None
+        self.base_quantization = None
+        self.invalidate_weight_cache()
+
     @property
     def has_active_lora(self) -> bool:
         return self.lora is not None and self.lora_enabled
@@ -243,6 +306,10 @@ class Linear(nn.Module):
         lo = self.lora
         if lo is None:
             return
+        if self.qweight is not None:
+            raise RuntimeError("merge_lora: this linear's base is quantized (--base_quantization); "
+                               "merge the adapter into the 16-bit checkpoint instead "
+                               "(scripts/merge_lora.py)")
         W = self.weight
         for (n_off, n_len, r_off, b_off) in lo.segs:
             A = lo.lora_A[r_off:r_off + lo.r].float()
@@ -288,7 +355,8 @@ def configure_backward_layout(model: nn.Module, policy=None) -> int:
             head_ok = not name.endswith("lm_head") or os.environ.get("LUMEN_LMHEAD_WT", "1") != "0"
             on = head_ok and (names is None or m.seg_names[0] in names)
             gathered = getattr(m.weight, "_lumen_gathered", False)
-            if on and not gathered:  # persistent copies must fit the HBM budget
+            # (a quantized base keeps no W^T: dequant_into writes it per use, nothing to budget)
+            if on and not gathered and m.qweight is None:  # persistent copies must fit the HBM budget
                 need = m.weight.numel() * m.weight.element_size()
                 on = need <= budget
                 budget -= need if on else 0
@@ -316,6 +384,48 @@ def _transpose_budget(model: nn.Module) -> float:
     from ..parallel.memory_plan import activation_reserve
 
     return max(0.0, free - activation_reserve(total, "LUMEN_BWD_WT_RESERVE_GB"))
+
+
+# the decoder projections --base_quantization stores quantized: the set serving quantizes (Llama's
+# q|k|v, o, gate|up, down; OPT's q|k|v, out_proj, fc1, fc2).  Embeddings, norms and the LM head
+# stay 16-bit.
+BASE_QUANT_PROJECTIONS = ("qkv_proj", "o_proj", "gate_up_proj", "down_proj", "out_proj", "fc1",
+                          "fc2")
+
+
+def quantize_base_model(model: nn.Module, kind: str) -> int:
+    """``Linear.quantize_base(kind)`` on every decoder projection of ``model``, one at a time, each
+    freeing its 16-bit storage before the next is quantized (peak memory: the 16-bit model plus
+    one projection's f32 temporaries).  Runs after the weights are loaded or initialised and before
+    ``apply_lora`` and the engine.  Returns the number of linears quantized."""
+    if kind not in BASE_QUANT_KINDS:
+        raise ValueError(f"base quantization must be one of {BASE_QUANT_KINDS}, got {kind!r}")
+    n = 0
+    for name, m in model.named_modules():
+        leaf = name.rsplit(".", 1)[-1]
+        if isinstance(m, Linear) and ".layers." in "." + name and leaf in BASE_QUANT_PROJECTIONS:
+            if m.lora is not None:
+                raise RuntimeError("quantize_base_model runs before apply_lora")
+            m.quantize_base(kind, leaf)
+            n += 1
+    if n == 0:
+        raise RuntimeError("quantize_base_model found no decoder projection to quantize")
+    model.base_quantization = kind
+    return n
+
+
+def dequantize_base_model(model: nn.Module) -> None:
+    """Undo ``quantize_base_model``'s storage (not its rounding): every quantized projection back
+    to a 16-bit weight holding ``dequant()`` (evaluation merges adapters into that)."""
+    for m in model.modules():
+        if isinstance(m, Linear):
+            m.dequantize_base()
+    model.base_quantization = None
+
+
+def base_quantization_of(model: nn.Module) -> str:
+    """"none", "fp8" or "mxfp4": how ``model``'s frozen decoder projections are stored."""
+    return getattr(model, "base_quantization", None) or "none"
 
 
 def invalidate_weight_caches(model: nn.Module) -> None:

@@ -698,3 +698,81 @@ def swiglu_linear_nt(gu: torch.Tensor, w) -> torch.Tensor:
         native().skinny_swiglu_gemm(gu, w, y)
         return y
     return linear_nt(swiglu(gu), w)
+
+
+# ---- quantized frozen base for training (--base_quantization, kernels/qbase.hip) ---------------
+# The frozen projections are stored once, as a weight-only QuantWeight / Mxfp4Weight, and
+# dequantised per use into a 16-bit scratch: "nk" = [N, K] for the forward and the NN backward,
+# "kn" = [K, N] = W^T for the TN input-gradient GEMM.  The library GEMMs stay as they are.
+#
+# The pool is separate from the serving scratch above (that one is sized by w8_reserve and
+# captured in decode graphs).  One buffer per (device, stream, dtype, projection name, layout),
+# shared by every layer and sized to the largest user: weights that one layer's forward or
+# backward touches never alias each other, and consecutive layers reuse a buffer in stream order
+# (8 buffers for a Llama layer, ~0.8 GB on Llama-2-7B).  A view is valid until the next
+# dequant_into of the same key.
+QBASE_LAYOUTS = ("nk", "kn")
+_qbase_pool: dict = {}
+
+
+def qbase_check_shape(N: int, K: int) -> None:
+    """The shapes the training dequantisers take (every Llama / OPT preset projection)."""
+    if K % 16 or N % 8 or K < 16 or N < 8:
+        raise ValueError(f"a quantized base needs projections with K % 16 == 0 and N % 8 == 0, "
+                         f"got [N, K] = [{N}, {K}]")
+
+
+def qbase_scratch_bytes(device=None) -> int:
+    """Bytes the training dequant pool holds (on ``device``, or everywhere)."""
+    return sum(b.numel() * b.element_size() for k, b in _qbase_pool.items()
+               if device is None or k[0] == str(device))
+
+
+def qbase_release() -> None:
+    """Drop the training dequant pool (tests, and between benchmark configurations)."""
+    _qbase_pool.clear()
+
+
+def _qbase_scratch(w, layout: str, name: str) -> torch.Tensor:
+    N, K = w.shape
+    key = _dg_key(w.device) + (w.dtype, name, layout)
+    buf = _qbase_pool.get(key)
+    if buf is None or buf.numel() < N * K:
+        # the superseded buffer is freed by the caching allocator in stream order
+        buf = torch.empty(N * K, dtype=w.dtype, device=w.device)
+        _qbase_pool[key] = buf
+    return buf[:N * K].view((N, K) if layout == "nk" else (K, N))
+
+
+def qbase_dequant(w, out: torch.Tensor) -> torch.Tensor:
+    """``out[:, :K]`` ([N, K] view, row stride ld >= K, ld % 8 == 0) = ``w.dequant()``, bit for
+    bit; columns K..ld are not written."""
+    native().qbase_dequant(w.q, w.scale, out, out.stride(0))
+    return out
+
+
+def qbase_dequant_t(w, out: torch.Tensor) -> torch.Tensor:
+    """``out`` (contiguous [K, N]) = ``w.dequant().t()``, bit for bit."""
+    native().qbase_dequant_t(w.q, w.scale, out)
+    return out
+
+
+def dequant_into(w, layout: str = "nk", name: Optional[str] = None) -> torch.Tensor:
+    """The 16-bit weight of the weight-only holder ``w``: ``w.dequant()`` ("nk") or its
+    transpose ("kn").  On the GPU a view of the training scratch of (device, stream, dtype,
+    ``name``, layout) -- ``name`` is the projection's name, by default ``w.name`` or the shape --
+    valid until the next call with the same key; elsewhere a fresh tensor."""
+    if layout not in QBASE_LAYOUTS:
+        raise ValueError(f"layout must be one of {QBASE_LAYOUTS}, got {layout!r}")
+    if not isinstance(w, (QuantWeight, Mxfp4Weight)) or w.act is not None:
+        raise ValueError("dequant_into takes a weight-only QuantWeight or Mxfp4Weight")
+    if not use_native(w.q):
+        d = w.dequant()
+        return d if layout == "nk" else d.t().contiguous()
+    if w.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"a quantized base on the GPU needs a 16-bit model dtype, got {w.dtype}")
+    qbase_check_shape(*w.shape)
+    if name is None:
+        name = getattr(w, "name", None) or f"{w.shape[0]}x{w.shape[1]}"
+    out = _qbase_scratch(w, layout, name)
+    return qbase_dequant(w, out) if layout == "nk" else qbase_dequant_t(w, out)

@@ -140,6 +140,86 @@ def lora_numel(cfg, lora_r: int = 16, targets=("q_proj", "k_proj", "v_proj", "o_
                                        if t in targets)
 
 
+def _llama_linears(cfg) -> List[tuple]:
+    """(name, N, K) of a Llama decoder layer's projections."""
+    H, Fd = cfg.hidden_size, cfg.intermediate_size
+    q, kv = cfg.num_attention_heads * cfg.head_dim, cfg.num_key_value_heads * cfg.head_dim
+    return [("qkv_proj", q + 2 * kv, H), ("o_proj", H, q), ("gate_up_proj", 2 * Fd, H),
+            ("down_proj", H, Fd)]
+
+
+def qbase_bytes(cfg, kind: str, elem_bytes: int = 2) -> float:
+    """Persistent bytes of the decoder projections under ``--base_quantization kind``: fp8 = one
+    byte per element + an f32 scale per row; mxfp4 = half a byte per element (rows padded to 32)
+    + one scale byte per 32; none = 16-bit."""
+    tot = 0.0
+    for _, n, k in _llama_linears(cfg):
+        if kind == "fp8":
+            tot += n * k + 4 * n
+        elif kind == "mxfp4":
+            kb = -(-k // 32)
+            tot += n * kb * 17
+        else:
+            tot += n * k * elem_bytes
+    return tot * cfg.num_hidden_layers
+
+
+def qbase_scratch_bytes(cfg, transposed: bool = True, elem_bytes: int = 2) -> float:
+    """The training dequant pool (ops/gemm.py dequant_into): one 16-bit [N, K] buffer per
+    projection name, and one more for W^T where the TN backward is on, shared by every layer."""
+    return float(sum(n * k for _, n, k in _llama_linears(cfg)) * elem_bytes
+                 * (2 if transposed else 1))
+
+
+def plan_replicated(cfg, hbm_bytes: float, tokens: int, base_quantization: str = "none",
+                    checkpointing="auto", lora_r: int = 16,
+                    lora_targets=("q_proj", "k_proj", "v_proj", "o_proj"), world: int = 1,
+                    elem_bytes: int = 2) -> Dict:
+    """Planned peak HBM of a rank whose frozen base is replicated (ZeRO stage 0 / 1 / 2), 16-bit
+    or quantized.  16-bit: every projection twice (W and the W^T of the TN backward, while it fits
+    under the reserve, all-or-nothing here) plus the LoRA fold's copies of the adapted ones;
+    quantized: the quantized bytes once plus the dequant
+    scratch.  Embedding and LM head (with its W^T) stay 16-bit either way."""
+    V, H = cfg.vocab_size, cfg.hidden_size
+    other = (2 + (1 if os.environ.get("LUMEN_LMHEAD_WT", "1") != "0" else 0)) * V * H * elem_bytes
+    n_lora = lora_numel(cfg, lora_r, lora_targets)
+    lora_state = n_lora * 8 + n_lora * 12 / max(world, 1)
+    base = qbase_bytes(cfg, base_quantization, elem_bytes)
+    fold = 0.0
+    if base_quantization in ("fp8", "mxfp4"):
+        wt, scratch = 0.0, qbase_scratch_bytes(cfg, True, elem_bytes)
+    else:
+        scratch = 0.0
+        # the LoRA fold's [W | s B_bd | 0] copies of the adapted linears (a quantized base has none)
+        if lora_r in (16, 32, 64):
+            seg = {"qkv_proj": ("q_proj", "k_proj", "v_proj"), "o_proj": ("o_proj",),
+                   "gate_up_proj": ("gate_proj", "up_proj"), "down_proj": ("down_proj",)}
+            fold = float(cfg.num_hidden_layers * elem_bytes * sum(
+                n * (k + 64) for name, n, k in _llama_linears(cfg)
+                if any(t in lora_targets for t in seg[name])))
+        base_free = hbm_bytes - RUNTIME_OVERHEAD - fold
+        free = base_free - base - other - lora_state
+        wt = base if base <= free - activation_reserve(hbm_bytes, "LUMEN_BWD_WT_RESERVE_GB") else 0.0
+    left = hbm_bytes - RUNTIME_OVERHEAD - base - other - lora_state - wt - scratch - fold
+    est = activation_bytes(cfg, tokens, "none")
+    if checkpointing == "auto":
+        policy = pick_checkpointing(est, left, selective_ok=not any(
+            t in lora_targets for t in ("gate_proj", "up_proj", "down_proj")),
+            n_layers=cfg.num_hidden_layers)
+    else:
+        policy = checkpointing
+    act = activation_bytes(cfg, tokens, policy or "none")
+    peak = RUNTIME_OVERHEAD + base + other + lora_state + wt + scratch + fold + act + TRANSIENT
+    return {"model": cfg.name, "base_quantization": base_quantization, "tokens": tokens,
+            "gb": {"runtime": RUNTIME_OVERHEAD / 1e9, "projections": base / 1e9,
+                   "embed_head": other / 1e9, "lora_state": lora_state / 1e9,
+                   "w_transposed": wt / 1e9, "lora_fold": fold / 1e9,
+                   "dequant_scratch": scratch / 1e9,
+                   "activations": act / 1e9, "transient": TRANSIENT / 1e9},
+            "checkpointing": policy or "none", "peak_gb": peak / 1e9,
+            "headroom": 1.0 - peak / hbm_bytes}
+
+
 def plan_zero3(cfg, world: int, hbm_bytes: float, tokens: int, checkpointing="auto",
                lora_r: int = 16, lora_targets=("q_proj", "k_proj", "v_proj", "o_proj"),
                elem_bytes: int = 2, align: int = 64) -> Dict:

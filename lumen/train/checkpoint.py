@@ -104,6 +104,16 @@ def save_checkpoint(output_dir: str, engine, model, trainer_state: Dict, env,
 def load_checkpoint(path: str, engine, model, env) -> Dict:
     with open(os.path.join(path, "latest")) as f:
         tag = f.read().strip()
+    # the adapters were trained over the base as it was stored then (--base_quantization):
+    # another storage is another base function, so resuming under it is refused
+    from ..models.layers import base_quantization_of
+
+    with open(os.path.join(path, "trainer_state.json")) as f:
+        saved = json.load(f).get("base_quantization") or "none"
+    if saved != base_quantization_of(model):
+        raise ValueError(f"checkpoint {path} was written with --base_quantization {saved}; "
+                         f"resuming with --base_quantization {base_quantization_of(model)} would "
+                         "train the adapters over a different base")
     load_adapter(model, path, apply=False)
     from .reshard import load_engine_state
 

@@ -80,6 +80,10 @@ class ZeroEngine:
         self.gather_group = None
         single = os.environ.get("LUMEN_ZERO3_SINGLE", "0") == "1"
         if self.stage >= 3:
+            if getattr(model, "base_quantization", None):
+                raise ValueError("a quantized frozen base (--base_quantization) does not support "
+                                 "ZeRO stage 3: the parameter coordinator owns the weight "
+                                 "storage there")
             if W > 1 and dist.is_initialized() and os.environ.get(
                     "LUMEN_ZERO3_SHARED_GROUP", "0") != "1":
                 # weight gathers on their own communicator (own RCCL stream): gradient

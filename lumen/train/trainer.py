@@ -65,6 +65,36 @@ class TrainArgs:
     log_file: Optional[str] = None
     async_save: bool = True
     fuse_accumulation: bool = True  # equal-size accumulation micro-batches as one forward
+    base_quantization: str = "none"  # none | fp8 | mxfp4: storage of the frozen decoder projections
+
+
+def check_base_quantization(kind: str, ds: DSConfig) -> None:
+    """Refuse, at startup, the configurations a quantized frozen base does not support."""
+    from ..models.layers import BASE_QUANT_KINDS
+
+    if kind == "none":
+        return
+    if kind not in BASE_QUANT_KINDS:
+        raise ValueError(f"--base_quantization must be none, fp8 or mxfp4, got {kind!r}")
+    if ds.stage == 3:
+        raise ValueError(f"--base_quantization {kind} does not support ZeRO stage 3 (the parameter "
+                         "coordinator owns the weight storage there); use stage 0, 1 or 2")
+    if ds.offload_param != "none":
+        raise ValueError(f"--base_quantization {kind} does not support offload_param")
+    from ..ops import activation, lora
+
+    def on(name, const):
+        return os.environ.get(name, "0") not in ("", "0") or bool(const)
+
+    if on("LUMEN_FUSED_MLP", activation.FUSED_MLP != "0"):
+        raise ValueError(f"--base_quantization {kind} does not support LUMEN_FUSED_MLP (its kernel "
+                         "reads the 16-bit weight in place)")
+    for name, const in (("LUMEN_MLP_OVERLAP", activation.MLP_OVERLAP),
+                        ("LUMEN_LORA_BWD_OVERLAP", lora.BWD_OVERLAP)):
+        if on(name, const):
+            raise ValueError(f"--base_quantization {kind} does not support {name} (it fetches a "
+                             "weight on one stream and uses it on another; the dequant scratch "
+                             "is per stream)")
 
 
 def model_flops_per_token(cfg, seq_len: int, lora: bool = True) -> float:
@@ -86,6 +116,7 @@ class Trainer:
 
             load_tuned_gemms()
         dt = ds.torch_dtype
+        check_base_quantization(args.base_quantization, ds)
         cfg = get_config(args.model_name)
         self.model_cfg = cfg
         t0 = time.time()
@@ -93,6 +124,11 @@ class Trainer:
                                  seed=args.seed)
         self.print(f"[lumen] model {cfg.name}: {cfg.num_params():,} params, dtype {dt}, "
                    f"built in {time.time() - t0:.1f}s")
+        if args.base_quantization != "none":
+            from ..models.layers import quantize_base_model
+
+            n = quantize_base_model(self.model, args.base_quantization)
+            self.print(f"[lumen] frozen base stored as {args.base_quantization}: {n} projections")
         lcfg = LoraConfig(r=args.lora_r, lora_alpha=args.lora_alpha, lora_dropout=args.lora_dropout,
                           target_modules=args.lora_targets)
         apply_lora(self.model, lcfg)
@@ -157,6 +193,16 @@ class Trainer:
         co = self.engine.coordinator
         if co is not None:
             free = max(0, free - co.pending_alloc_bytes())
+        if a.base_quantization != "none":
+            # the quantized projections are resident already and keep no W^T; what the first
+            # micro-step still allocates is the dequant scratch pool
+            from ..models.layers import Linear
+            from ..ops.gemm import qbase_scratch_bytes as pool_bytes
+            from ..parallel.memory_plan import qbase_scratch_bytes
+
+            tn = any(m.transpose_bwd for m in self.model.modules()
+                     if isinstance(m, Linear) and m.qweight is not None)
+            free = max(0, free - max(0.0, qbase_scratch_bytes(cfg, tn) - pool_bytes(env.device)))
         pols = getattr(type(self.model), "CKPT_POLICIES", None)
         # selective only where every layer's MLP can recompute (frozen, unadapted gate|up/down)
         sel_ok = bool(pols and "selective" in pols
@@ -435,6 +481,7 @@ class Trainer:
                 "batches_in_epoch": getattr(self, "_batches_in_epoch", 0) if samples_in_epoch else 0,
                 "log_history": self.log_history,
                 "world_size": self.env.world_size, "zero_stage": self.ds.stage,
+                "base_quantization": self.args.base_quantization,
                 "train_batch_size": self.ds.train_batch_size, "args": asdict(self.args)}
 
     def _save(self, epoch: int, samples_in_epoch: int):

@@ -32,6 +32,9 @@ def main(argv=None):
     p.add_argument("--max_new_tokens", type=int, default=128)
     p.add_argument("--gen_samples", type=int, default=64)
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
+    p.add_argument("--base_quantization", default="none", choices=["none", "fp8", "mxfp4"],
+                   help="store the frozen decoder projections as training's --base_quantization "
+                        "did, so the adapter is evaluated over the base it saw")
     p.add_argument("--skip_loss", action="store_true")
     p.add_argument("--skip_generation", action="store_true")
     p.add_argument("--output", default=None)
@@ -68,11 +71,20 @@ def main(argv=None):
     model = build_model(a.model, dtype=dt, device=dev)
     tok = load_tokenizer(a.adapter if a.adapter and os.path.isfile(
         os.path.join(a.adapter, "tokenizer_config.json")) else a.model, model.config.vocab_size)
-    if a.adapter:
-        from lumen.lora import load_adapter
+    if a.base_quantization != "none":
+        from lumen.models.layers import quantize_base_model
 
+        quantize_base_model(model, a.base_quantization)
+    if a.adapter:
+        from lumen.lora import load_adapter, read_base_quantization
+
+        trained = read_base_quantization(a.adapter)
+        if trained != a.base_quantization and rank == 0:
+            print(f"warning: {a.adapter} was trained with --base_quantization {trained}, "
+                  f"evaluating with {a.base_quantization}", file=sys.stderr)
         load_adapter(model, a.adapter)
-    out = {"model": a.model, "adapter": a.adapter, "samples": len(texts)}
+    out = {"model": a.model, "adapter": a.adapter, "samples": len(texts),
+           "base_quantization": a.base_quantization}
 
     if not a.skip_loss:
         enc = tok(texts, truncation=True, max_length=a.max_length, padding=False)
@@ -88,6 +100,11 @@ def main(argv=None):
         pairs = [split_llama2_chat(t) for t in texts[: a.gen_samples]]
         pairs = [(q, r) for q, r in pairs if r]
         if pairs:
+            if a.base_quantization != "none":
+                # the same base function in 16 bits (W = dequant()), which the merge can add to
+                from lumen.models.layers import dequantize_base_model
+
+                dequantize_base_model(model)
             merge_lora(model)  # serving runs on merged weights (adapters folded in)
             max_len = a.max_length + a.max_new_tokens
             eng = LLMEngine(EngineConfig(model=a.model, dtype=a.dtype, max_model_len=max_len,
