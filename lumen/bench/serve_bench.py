@@ -52,8 +52,7 @@ def make_engine(a):
     if torch.cuda.is_available():
         # what the weights leave for the KV cache: before / after the cache was allocated
         free = torch.cuda.mem_get_info()[0]
-        kv = sum(t.numel() * t.element_size() for t in list(eng.runner.k_cache)
-                 + list(eng.runner.v_cache))
+        kv = sum(t.nbytes for t in list(eng.runner.k_cache) + list(eng.runner.v_cache))
         eng._bench_hbm = {"free_after_setup_gib": round(free / 2 ** 30, 2),
                           "kv_cache_gib": round(kv / 2 ** 30, 2)}
     return eng
@@ -284,7 +283,7 @@ def main():
     ap.add_argument("--prefill-boost", type=int, default=1,
                     help="x token budget while at most max-num-seqs/4 sequences decode (1: off)")
     ap.add_argument("--no-graphs", action="store_true")
-    ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8"])
+    ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8", "mxfp4"])
     ap.add_argument("--quantization", default=None,
                     choices=["fp8", "ptpc_fp8", "mxfp4", "mxfp4_a16"],
                     help="quantization of the decoder projections: fp8 = weight-only, "

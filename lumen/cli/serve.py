@@ -54,8 +54,10 @@ def build_parser():
     ap.add_argument("--block-size", type=int, default=16)
     ap.add_argument("--gpu-memory-utilization", type=float, default=0.9)
     ap.add_argument("--no-graphs", action="store_true")
-    ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8"],
-                    help="KV-cache element type (fp8 = e4m3: 2x capacity, half the decode K/V reads)")
+    ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8", "mxfp4"],
+                    help="KV-cache element type (fp8 = e4m3: 2x capacity, half the decode K/V reads; "
+                         "mxfp4 = e2m1 codes + E8M0 block scales, 4.25 bits: 3.76x capacity, "
+                         "round-to-nearest and uncalibrated)")
     ap.add_argument("--quantization", default=None, choices=["fp8", "ptpc_fp8", "mxfp4", "mxfp4_a16"],
                     help="quantization (vLLM's flag): fp8 = decoder projections stored as e4m3 "
                          "with per-output-row scales, 16-bit activations; ptpc_fp8 = the same "

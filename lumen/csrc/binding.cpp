@@ -113,6 +113,8 @@ hipError_t lumen_paged_attention_decode(int, void*, const void*, const void*, co
                                         int, hipStream_t);
 hipError_t lumen_kv_dequant(int, const void*, const void*, void*, void*, const int*, int,
                             const int*, int, int, int, int, int, hipStream_t);
+hipError_t lumen_kv_dequant_mx(int, const void*, const void*, void*, void*, const int*, int,
+                               const int*, int, int, int, int, int, hipStream_t);
 hipError_t lumen_reshape_and_cache(int, const void*, const void*, void*, void*, const long long*,
                                    int, int, int, int, long long, long long, int, hipStream_t);
 hipError_t lumen_sample(int, const void*, const float*, const float*, const int*,
@@ -866,6 +868,19 @@ void lora2(int64_t dtype, int64_t kind, int64_t flag, const at::Tensor& big, int
 
 bool is_fp8(const at::Tensor& t) { return t.scalar_type() == at::kFloat8_e4m3fn; }
 
+// The type of a paged K / V cache, as the kernels number it: 0 = the model dtype and 1 = fp8
+// e4m3fn, both [nb, nkv, bs, D]; 2 = mxfp4, uint8 [nb, nkv, bs * (D/2 + D/32)] (per block and
+// head the rows' e2m1 codes, then their E8M0 scale bytes: lumen.ops.attention.Mxfp4KV.buf).
+int kv_kind(const at::Tensor& c, int64_t nkv, int64_t bs, int64_t D, const char* who) {
+  if (c.scalar_type() != at::kByte) return is_fp8(c) ? 1 : 0;
+  const int64_t ch = bs * (D / 2 + D / 32);
+  if (D % 32 != 0 || ch % 4 != 0 || c.dim() != 3 || !c.is_contiguous() || c.size(1) != nkv ||
+      c.size(2) != ch)
+    throw std::invalid_argument(std::string("lumen: ") + who + ": an mxfp4 cache is a contiguous "
+                                "uint8 [nb, nkv, bs * (D/2 + D/32)] with D % 32 == 0");
+  return 2;
+}
+
 void need_cuda_f32(const at::Tensor& t, const char* what) {
   if (!t.is_cuda() || t.scalar_type() != at::kFloat)
     throw std::invalid_argument(std::string("lumen: ") + what + " must be an f32 GPU tensor");
@@ -1142,7 +1157,9 @@ void paged_attention_decode(at::Tensor& out, const at::Tensor& q, const at::Tens
                                      static_cast<int>(tmp_m.size(-1)), static_cast<float>(scale),
                                      tmp_m.data_ptr<float>(), tmp_l.data_ptr<float>(),
                                      tmp_o.data_ptr(), static_cast<int>(partition_size), cnt,
-                                     static_cast<int>(one_pass), is_fp8(k_cache) ? 1 : 0, qldh,
+                                     static_cast<int>(one_pass),
+                                     kv_kind(k_cache, num_kv_heads, block_size, D,
+                                             "paged_attention_decode"), qldh,
                                      cur_stream()),
         "paged_attention_decode");
 }
@@ -1170,6 +1187,31 @@ void kv_dequant(const at::Tensor& k_cache, const at::Tensor& v_cache, at::Tensor
         "kv_dequant");
 }
 
+// mxfp4 KV cache -> 16-bit scratch [>= nseq * maxb, nkv, bs, D], as kv_dequant
+void kv_dequant_mx(const at::Tensor& k_cache, const at::Tensor& v_cache, at::Tensor& k_scr,
+                   at::Tensor& v_scr, const at::Tensor& tables, const at::Tensor& kv_lens,
+                   int64_t maxb) {
+  need_cuda(k_cache, "k_cache"); need_cuda(v_cache, "v_cache");
+  need_cuda(k_scr, "k_scr"); need_cuda(v_scr, "v_scr");
+  need_cuda(tables, "tables"); need_cuda(kv_lens, "kv_lens");
+  if (k_scr.dim() != 4 || tables.scalar_type() != at::kInt || kv_lens.scalar_type() != at::kInt ||
+      tables.dim() != 2 || tables.size(0) < kv_lens.numel() || tables.size(1) < maxb ||
+      k_scr.size(0) < kv_lens.numel() * maxb || !k_scr.is_contiguous() ||
+      !v_scr.is_contiguous() || v_scr.sizes() != k_scr.sizes() ||
+      v_scr.scalar_type() != k_scr.scalar_type() || v_cache.sizes() != k_cache.sizes() ||
+      kv_kind(k_cache, k_scr.size(1), k_scr.size(2), k_scr.size(3), "kv_dequant_mx") != 2 ||
+      kv_kind(v_cache, k_scr.size(1), k_scr.size(2), k_scr.size(3), "kv_dequant_mx") != 2)
+    throw std::invalid_argument("lumen: kv_dequant_mx: mxfp4 caches, 16-bit scratch [>= nseq * "
+                                "maxb, nkv, bs, D], int32 tables / kv_lens");
+  check(lumen_kv_dequant_mx(dcode(k_scr), k_cache.data_ptr(), v_cache.data_ptr(),
+                            k_scr.data_ptr(), v_scr.data_ptr(), tables.data_ptr<int>(),
+                            static_cast<int>(tables.stride(0)), kv_lens.data_ptr<int>(),
+                            static_cast<int>(kv_lens.numel()), static_cast<int>(maxb),
+                            static_cast<int>(k_scr.size(1)), static_cast<int>(k_scr.size(2)),
+                            static_cast<int>(k_scr.size(3)), cur_stream()),
+        "kv_dequant_mx");
+}
+
 void reshape_and_cache(const at::Tensor& k, const at::Tensor& v, at::Tensor& k_cache, at::Tensor& v_cache,
                        const at::Tensor& slot_mapping, int64_t num_kv_heads, int64_t D,
                        int64_t block_size, int64_t k_stride, int64_t v_stride) {
@@ -1178,7 +1220,8 @@ void reshape_and_cache(const at::Tensor& k, const at::Tensor& v, at::Tensor& k_c
                                 v_cache.data_ptr(), reinterpret_cast<const long long*>(slot_mapping.data_ptr<int64_t>()), ntok,
                                 static_cast<int>(num_kv_heads), static_cast<int>(D),
                                 static_cast<int>(block_size), k_stride, v_stride,
-                                is_fp8(k_cache) ? 1 : 0, cur_stream()),
+                                kv_kind(k_cache, num_kv_heads, block_size, D, "reshape_and_cache"),
+                                cur_stream()),
         "reshape_and_cache");
 }
 
@@ -1201,7 +1244,8 @@ void rope_cache_write(at::Tensor& qkv, const at::Tensor& pos, const at::Tensor& 
                          reinterpret_cast<const long long*>(slots.data_ptr<int64_t>()),
                          static_cast<int>(qkv.size(0)), static_cast<int>(nh),
                          static_cast<int>(nkv), static_cast<int>(D),
-                         static_cast<int>(block_size), is_fp8(k_cache) ? 1 : 0, cur_stream()),
+                         static_cast<int>(block_size),
+                         kv_kind(k_cache, nkv, block_size, D, "rope_cache_write"), cur_stream()),
         "rope_cache_write");
 }
 
@@ -1448,6 +1492,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("lora3_z_tail", &lora3_z_tail);
   m.def("lora3_w_tail", &lora3_w_tail);
   m.def("kv_dequant", &kv_dequant);
+  m.def("kv_dequant_mx", &kv_dequant_mx);
   m.def("lora3_up", &lora3_up);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("qkv_rope", &qkv_rope);

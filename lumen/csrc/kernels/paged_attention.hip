@@ -15,6 +15,7 @@
 // is one wave per head; P.V accumulates per lane then reduces through LDS.  Contexts longer than
 // one partition write unnormalised (m, l, o) partials that `pa_reduce_kernel` merges.
 #include "common.h"
+#include "mxfp4.h"
 
 #include <type_traits>
 
@@ -26,6 +27,47 @@ constexpr int kMaxGroup = 8;
 // gfx950 packed converts (v_cvt_pk_f32_fp8 / v_cvt_pk_fp8_f32), no scale (vLLM's uncalibrated
 // default of 1.0).  Halves the K/V bytes every decode step streams.
 using fp8 = unsigned char;
+
+// MXFP4 KV cache (--kv-cache-dtype mxfp4): one (block, kv-head) is a chunk of BS * (D/2 + D/32)
+// bytes -- the BS rows' e2m1 codes (D/2 bytes a row, the even element in the low nibble), then
+// the BS rows' E8M0 block-scale bytes (D/32 a row) -- so codes and scales share the block id and
+// a row's codes stay 16-byte aligned.  Exactly ops/quant.py's quantize_mxfp4_rows of each row.
+struct mxkv { unsigned char b; };
+
+template <typename KT> constexpr bool is_mx() { return std::is_same<KT, mxkv>::value; }
+
+// bytes (mxkv) or elements (other caches) of one (block, kv-head) chunk
+template <typename KT>
+__device__ __forceinline__ size_t kv_chunk(int BS, int D) {
+  if constexpr (is_mx<KT>()) return static_cast<size_t>(BS) * (D / 2 + D / 32);
+  else return static_cast<size_t>(BS) * D;
+}
+
+// the piece of row `row` at elements [d0, d0 + 8) of an mxkv chunk: x = the code word, y = the
+// scale byte of the 32-element block it lies in
+template <bool NT>
+__device__ __forceinline__ uint2 mx_ld(const mxkv* __restrict__ chunk, int BS, int D, int row,
+                                       int d0) {
+  const unsigned* cp = reinterpret_cast<const unsigned*>(chunk + row * (D / 2) + d0 / 2);
+  const unsigned char* sp = &chunk[BS * (D / 2) + row * (D / 32) + d0 / 32].b;
+  if constexpr (NT) return make_uint2(__builtin_nontemporal_load(cp), __builtin_nontemporal_load(sp));
+  else return make_uint2(*cp, *sp);
+}
+
+// quantize 8 elements whose block's largest magnitude is amax; `lead`: this lane stores the byte
+__device__ __forceinline__ void mx_st(mxkv* __restrict__ chunk, int BS, int D, int row, int d0,
+                                      const float (&v)[8], float amax, bool lead) {
+  const unsigned e = mx::scale_byte(amax);
+  *reinterpret_cast<unsigned*>(chunk + row * (D / 2) + d0 / 2) = mx::encode8(v, e);
+  if (lead) chunk[BS * (D / 2) + row * (D / 32) + d0 / 32].b = static_cast<unsigned char>(e);
+}
+
+__device__ __forceinline__ float amax8(const float (&v)[8]) {
+  float m = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v[j]));
+  return m;
+}
 
 template <typename T, typename KT>
 __device__ __forceinline__ void load8kv(const KT* __restrict__ p, float (&o)[8]) {
@@ -52,6 +94,8 @@ __device__ __forceinline__ void cvt8kv(const R& r, float (&o)[8]) {
     const auto d = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(r.y), true);
     o[0] = a[0]; o[1] = a[1]; o[2] = b[0]; o[3] = b[1];
     o[4] = c[0]; o[5] = c[1]; o[6] = d[0]; o[7] = d[1];
+  } else if constexpr (is_mx<KT>()) {
+    mx::cvt8f(r.x, mx::e8m0_f32(r.y), o);
   } else {
     const T* e = reinterpret_cast<const T*>(&r);
 #pragma unroll
@@ -91,6 +135,14 @@ __device__ __forceinline__ float pa_red16(float v) {
   v += pa_dpp<0x141>(v);
   v += pa_dpp<0x140>(v);
   return v;
+}
+
+// largest |x| of an MX block held by 4 adjacent lanes (8 elements each), or by 2 (PAIR)
+template <bool PAIR = false>
+__device__ __forceinline__ float mx_group_max(float m) {
+  m = fmaxf(m, pa_dpp<0xB1>(m));
+  if constexpr (!PAIR) m = fmaxf(m, pa_dpp<0x4E>(m));
+  return m;
 }
 
 __device__ __forceinline__ void st_agent(float* p, float v) {
@@ -361,9 +413,17 @@ __global__ void __launch_bounds__(256) pa_decode1_kernel(
   // per lane each); 8 of fp8 rows (8 bytes each), so an fp8 cache keeps the same bytes in flight
   // (with 4 it streamed at ~3.9 TB/s against the bf16 cache's 5.9; 8 16-bit rows per lane
   // measured 26.9 vs 19.7 ms per 256-row decode step: the registers cost the occupancy)
+  // An mxfp4 row piece is a 4-byte code word plus its block's scale byte, each in one register
+  // (uint2, as the fp8 piece): 8 rows in flight cost the fp8 path's registers and the same
+  // number of converts per row.  (16 rows, the fp8 path's bytes in flight, measured slower: 182.8
+  // vs 160.0 us per layer at 256 sequences x 576 tokens, 32 kv heads, against fp8's 194 -- the
+  // path is bound by its load and convert issue, not by bytes in flight; profiles/kv_mxfp4.)
+  // No PF form (its asm loads would need two per piece).
   constexpr bool F8 = std::is_same<KT, fp8>::value;
-  constexpr int U = F8 ? 8 : 4;
-  using Raw = typename std::conditional<F8, uint2, uint4>::type;
+  constexpr bool MX = is_mx<KT>();
+  constexpr int U = (F8 || MX) ? 8 : 4;
+  using Raw = typename std::conditional<F8 || MX, uint2, uint4>::type;
+  static_assert(!(MX && PF), "no software-pipelined form over the mxfp4 cache");
   __shared__ float wst[4][G][D + 2];  // per-wave merged state: acc[D], m, l
   const int seq = blockIdx.x, kvh = blockIdx.y, part = blockIdx.z;
   const int ctx = context_lens[seq];
@@ -380,8 +440,8 @@ __global__ void __launch_bounds__(256) pa_decode1_kernel(
     for (int j = 0; j < 8; ++j) qv[h][j] *= scale;
   }
   const int* bt = block_tables + static_cast<size_t>(seq) * max_blocks;
-  const size_t head_off = static_cast<size_t>(kvh) * BS * D;
-  const size_t blk_stride = static_cast<size_t>(nkv) * BS * D;
+  const size_t head_off = static_cast<size_t>(kvh) * kv_chunk<KT>(BS, D);
+  const size_t blk_stride = static_cast<size_t>(nkv) * kv_chunk<KT>(BS, D);
   float m[G], l[G], acc[G][8];
 #pragma unroll
   for (int h = 0; h < G; ++h) {
@@ -485,23 +545,38 @@ __global__ void __launch_bounds__(256) pa_decode1_kernel(
       const int nb = base + NGR * U;
 #pragma unroll
       for (int u = 0; u < U; ++u) nbid[u] = nb + u * NGR < end ? bt[nb / NGR + u] : 0;
-      const KT* kr0 = kc + head_off + static_cast<size_t>(grp) * D + d0;
-      const KT* vr0 = vc + head_off + static_cast<size_t>(grp) * D + d0;
-      // unconditional (see the PF form): all 2U pieces in flight before the first use
+      if constexpr (MX) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const size_t off = static_cast<size_t>(bid[u]) * blk_stride;
-        kraw[u] = pa_ld_nt<Raw>(kr0 + off);
-        vraw[u] = pa_ld_nt<Raw>(vr0 + off);
+        for (int u = 0; u < U; ++u) {
+          const size_t off = static_cast<size_t>(bid[u]) * blk_stride + head_off;
+          kraw[u] = mx_ld<true>(kc + off, BS, D, grp, d0);
+          vraw[u] = mx_ld<true>(vc + off, BS, D, grp, d0);
+        }
+      } else {
+        const KT* kr0 = kc + head_off + static_cast<size_t>(grp) * D + d0;
+        const KT* vr0 = vc + head_off + static_cast<size_t>(grp) * D + d0;
+        // unconditional (see the PF form): all 2U pieces in flight before the first use
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const size_t off = static_cast<size_t>(bid[u]) * blk_stride;
+          kraw[u] = pa_ld_nt<Raw>(kr0 + off);
+          vraw[u] = pa_ld_nt<Raw>(vr0 + off);
+        }
       }
     } else {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int t = t0 + u * NGR;
         if (t < end) {
-          const size_t off = bt[t / BS] * blk_stride + head_off + (t % BS) * D + d0;
-          kraw[u] = *reinterpret_cast<const Raw*>(kc + off);
-          vraw[u] = *reinterpret_cast<const Raw*>(vc + off);
+          if constexpr (MX) {
+            const size_t off = bt[t / BS] * blk_stride + head_off;
+            kraw[u] = mx_ld<false>(kc + off, BS, D, t % BS, d0);
+            vraw[u] = mx_ld<false>(vc + off, BS, D, t % BS, d0);
+          } else {
+            const size_t off = bt[t / BS] * blk_stride + head_off + (t % BS) * D + d0;
+            kraw[u] = *reinterpret_cast<const Raw*>(kc + off);
+            vraw[u] = *reinterpret_cast<const Raw*>(vc + off);
+          }
         }
       }
     }
@@ -592,7 +667,17 @@ __global__ void __launch_bounds__(256) cache_write_kernel(
   if (slot < 0) return;
   const long long blk = slot / BS, off = slot % BS;
   const size_t dst = ((static_cast<size_t>(blk) * nkv + h) * BS + off) * D + c * 8;
-  if constexpr (std::is_same<KT, fp8>::value) {
+  if constexpr (is_mx<KT>()) {
+    // D % 32 == 0 (the launcher checks): the 4 lanes of an MX block are one aligned quad, all of
+    // them here (one token, one head)
+    float a[8], b[8];
+    load8(k + t * k_stride + static_cast<long long>(h) * D + c * 8, a);
+    load8(v + t * v_stride + static_cast<long long>(h) * D + c * 8, b);
+    const size_t chunk = (static_cast<size_t>(blk) * nkv + h) * kv_chunk<KT>(BS, D);
+    const int row = static_cast<int>(off);
+    mx_st(kc + chunk, BS, D, row, c * 8, a, mx_group_max(amax8(a)), (c & 3) == 0);
+    mx_st(vc + chunk, BS, D, row, c * 8, b, mx_group_max(amax8(b)), (c & 3) == 0);
+  } else if constexpr (std::is_same<KT, fp8>::value) {
     float a[8], b[8];
     load8(k + t * k_stride + static_cast<long long>(h) * D + c * 8, a);
     load8(v + t * v_stride + static_cast<long long>(h) * D + c * 8, b);
@@ -604,6 +689,25 @@ __global__ void __launch_bounds__(256) cache_write_kernel(
     *reinterpret_cast<uint4*>(vc + dst) =
         *reinterpret_cast<const uint4*>(v + t * v_stride + static_cast<long long>(h) * D + c * 8);
   }
+}
+
+// rope_cache_kernel's lane holds elements [i0, i0 + 8) and [i0 + D/2, i0 + D/2 + 8) of a head row.
+// D % 64 == 0: the MX blocks of each half are aligned lane quads.  D == 32: the row is one block,
+// held by a lane pair.  (The launcher admits no other D over an mxfp4 cache.)
+__device__ __forceinline__ void mx_rope_st(mxkv* __restrict__ cache, long long slot, int hk,
+                                           int nkv, int BS, int D, int i0, const float (&a)[8],
+                                           const float (&b)[8]) {
+  mxkv* chunk = cache + (static_cast<size_t>(slot / BS) * nkv + hk) * kv_chunk<mxkv>(BS, D);
+  const int row = static_cast<int>(slot % BS), half = D / 2;
+  float ma = amax8(a), mb = amax8(b);
+  if (D == 32) {
+    ma = mb = mx_group_max<true>(fmaxf(ma, mb));
+  } else {
+    ma = mx_group_max(ma);
+    mb = mx_group_max(mb);
+  }
+  mx_st(chunk, BS, D, row, i0, a, ma, i0 % 32 == 0);
+  mx_st(chunk, BS, D, row, i0 + half, b, mb, (i0 + half) % 32 == 0);
 }
 
 // RoPE of the q and k heads of the fused token-major QKV rows AND the paged KV-cache write of
@@ -643,11 +747,29 @@ __global__ void __launch_bounds__(256) rope_cache_kernel(
     }
     store8(row + i0, oa);
     store8(row + i0 + half, ob);
+    if constexpr (is_mx<KT>()) {
+      if (h >= nh && slot >= 0) {
+        // the cache holds the quantization of the 16-bit k just written back, not of the f32
+        // rotation: identical to RoPE followed by the plain cache write
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          oa[j] = to_f32(from_f32<T>(oa[j]));
+          ob[j] = to_f32(from_f32<T>(ob[j]));
+        }
+        mx_rope_st(kc, slot, hk, nkv, BS, D, i0, oa, ob);
+      }
+    } else
     if (h >= nh && slot >= 0) {
       store8kv<T, KT>(kc + dst + i0, oa);
       store8kv<T, KT>(kc + dst + i0 + half, ob);
     }
   } else if (slot >= 0) {
+    if constexpr (is_mx<KT>()) {
+      float a[8], b[8];
+      load8(row + i0, a);
+      load8(row + i0 + half, b);
+      mx_rope_st(vc, slot, hk, nkv, BS, D, i0, a, b);
+    } else
     if constexpr (std::is_same<KT, fp8>::value) {
       float a[8], b[8];
       load8(row + i0, a);
@@ -684,6 +806,28 @@ __global__ void __launch_bounds__(256) kv_dequant_kernel(
   }
 }
 
+// the same over an mxfp4 cache: exact in bf16 (every e2m1 x 2^e is a bf16 number), one rounding
+// in fp16 (v_cvt_scalef32_pk_{bf16,f16}_fp4)
+template <typename T>
+__global__ void __launch_bounds__(256) kv_dequant_mx_kernel(
+    const mxkv* __restrict__ kc, const mxkv* __restrict__ vc, T* __restrict__ ks,
+    T* __restrict__ vs, const int* __restrict__ tables, int tstride, const int* __restrict__ kv_lens,
+    int maxb, int nkv, int BS, int D) {
+  const int s = blockIdx.x, b = blockIdx.y;
+  if (b * BS >= kv_lens[s]) return;
+  const size_t ch = kv_chunk<mxkv>(BS, D);
+  const mxkv* src = (blockIdx.z == 0 ? kc : vc) +
+                    static_cast<size_t>(tables[static_cast<size_t>(s) * tstride + b]) * nkv * ch;
+  T* dst = (blockIdx.z == 0 ? ks : vs) + (static_cast<size_t>(s) * maxb + b) * nkv * BS * D;
+  const int per_head = BS * D / 8, n8 = nkv * per_head, lpr = D / 8;
+  for (int i = threadIdx.x; i < n8; i += 256) {
+    const int h = i / per_head, r = (i % per_head) / lpr, d0 = (i % lpr) * 8;
+    const uint2 p = mx_ld<false>(src + h * ch, BS, D, r, d0);
+    *reinterpret_cast<uint4*>(dst + static_cast<size_t>(i) * 8) =
+        mx::cvt8<T>(p.x, mx::e8m0_f32(p.y));
+  }
+}
+
 // The PF kernel's inline-asm K / V loads are invisible to hipcc's register allocator, so a spill
 // or copy of a result before its counted wait would read stale data (scripts/tools/
 // check_asm_loads.py audits the code object).  The audit passes for D = 128 (every G) and G = 1
@@ -698,7 +842,7 @@ static void launch_pa_uni(bool pf, dim3 grid, hipStream_t st, void* out, const v
                           const void* kc, const void* vc, const int* bt, const int* cl, int nh,
                           int qldh, int nkv, int BS, int max_blocks, int max_parts, float scale,
                           float* tm, float* tl, void* to, int PART) {
-  if constexpr (pa_pf_ok<D, G>()) {
+  if constexpr (pa_pf_ok<D, G>() && !is_mx<KT>()) {  // (no PF form over the mxfp4 cache)
     if (pf) {
       hipLaunchKernelGGL((pa_decode1_kernel<T, D, G, KT, true, true>), grid, dim3(256), 0, st,
                          (T*)out, (const T*)q, (const KT*)kc, (const KT*)vc, bt, cl, nh, qldh, nkv,
@@ -716,12 +860,20 @@ static void launch_pa_g(int G, dim3 grid, size_t smem, hipStream_t st, void* out
                         const void* kc, const void* vc, const int* bt, const int* cl, int nh,
                         int qldh, int nkv, int BS, int max_blocks, int max_parts, float scale,
                         float* tm,
-                        float* tl, void* to, int PART, unsigned* cnt, int one_pass, bool fp8kv) {
+                        float* tl, void* to, int PART, unsigned* cnt, int one_pass, int kvk) {
+  const bool fp8kv = kvk == 1, mxk = kvk == 2;
   // one_pass 2: the uniform-block-id variant where the block size equals the rows per step
   const bool uni = one_pass >= 2 && BS == 256 / (D / 8) && PART % BS == 0;
   const bool pf = uni && one_pass == 3;
 #define LUMEN_PA_G(GG)                                                                         \
-  if (fp8kv && uni)                                                                             \
+  if (mxk && uni)                                                                               \
+    launch_pa_uni<T, D, GG, mxkv>(pf, grid, st, out, q, kc, vc, bt, cl, nh, qldh, nkv, BS,       \
+                                  max_blocks, max_parts, scale, tm, tl, to, PART);               \
+  else if (mxk)                                                                                 \
+    hipLaunchKernelGGL((pa_decode1_kernel<T, D, GG, mxkv>), grid, dim3(256), 0, st, (T*)out,    \
+                       (const T*)q, (const mxkv*)kc, (const mxkv*)vc, bt, cl, nh, qldh, nkv, BS,      \
+                       max_blocks, max_parts, scale, tm, tl, (float*)to, PART);                 \
+  else if (fp8kv && uni)                                                                             \
     launch_pa_uni<T, D, GG, fp8>(pf, grid, st, out, q, kc, vc, bt, cl, nh, qldh, nkv, BS,        \
                                  max_blocks, max_parts, scale, tm, tl, to, PART);                \
   else if (fp8kv)                                                                               \
@@ -753,14 +905,15 @@ static hipError_t launch_pa(void* out, const void* q, const void* kc, const void
                             void* to, int PART, unsigned* cnt, int one_pass, int fp8kv,
                             int qldh, hipStream_t st) {
   const int G = nh / nkv;
-  if (fp8kv && one_pass == 0) one_pass = 1;  // the fp8 cache: single-pass kernels only
+  if (fp8kv && one_pass == 0) one_pass = 1;  // fp8 / mxfp4 caches: single-pass kernels only
+  if (fp8kv == 2 && D % 32 != 0) return hipErrorInvalidValue;
   if (G != 1 && G != 2 && G != 4 && G != 8) return hipErrorInvalidValue;
   dim3 grid(nseq, nkv, max_parts);
   const size_t smem = (static_cast<size_t>(G) * PART + 4 * G * D + 2 * G + 8) * sizeof(float);
-  if (D == 128) launch_pa_g<T, 128>(G, grid, smem, st, out, q, kc, vc, bt, cl, nh, qldh, nkv, BS, max_blocks, max_parts, scale, tm, tl, to, PART, cnt, one_pass, fp8kv != 0);
-  else if (D == 64) launch_pa_g<T, 64>(G, grid, smem, st, out, q, kc, vc, bt, cl, nh, qldh, nkv, BS, max_blocks, max_parts, scale, tm, tl, to, PART, cnt, one_pass, fp8kv != 0);
-  else if (D == 256) launch_pa_g<T, 256>(G, grid, smem, st, out, q, kc, vc, bt, cl, nh, qldh, nkv, BS, max_blocks, max_parts, scale, tm, tl, to, PART, cnt, one_pass, fp8kv != 0);
-  else if (D == 32) launch_pa_g<T, 32>(G, grid, smem, st, out, q, kc, vc, bt, cl, nh, qldh, nkv, BS, max_blocks, max_parts, scale, tm, tl, to, PART, cnt, one_pass, fp8kv != 0);
+  if (D == 128) launch_pa_g<T, 128>(G, grid, smem, st, out, q, kc, vc, bt, cl, nh, qldh, nkv, BS, max_blocks, max_parts, scale, tm, tl, to, PART, cnt, one_pass, fp8kv);
+  else if (D == 64) launch_pa_g<T, 64>(G, grid, smem, st, out, q, kc, vc, bt, cl, nh, qldh, nkv, BS, max_blocks, max_parts, scale, tm, tl, to, PART, cnt, one_pass, fp8kv);
+  else if (D == 256) launch_pa_g<T, 256>(G, grid, smem, st, out, q, kc, vc, bt, cl, nh, qldh, nkv, BS, max_blocks, max_parts, scale, tm, tl, to, PART, cnt, one_pass, fp8kv);
+  else if (D == 32) launch_pa_g<T, 32>(G, grid, smem, st, out, q, kc, vc, bt, cl, nh, qldh, nkv, BS, max_blocks, max_parts, scale, tm, tl, to, PART, cnt, one_pass, fp8kv);
   else return hipErrorInvalidValue;
   if (max_parts > 1 && (cnt == nullptr || one_pass)) {  // unfused merge: second kernel
     dim3 g2(nseq, nh), b2(128);
@@ -781,6 +934,7 @@ extern "C" hipError_t lumen_paged_attention_decode(int dtype, void* out, const v
                                                    float* tmp_l, void* tmp_o, int PART,
                                                    unsigned* counters, int one_pass,
                                                    int fp8kv, int qldh, hipStream_t st) {
+  // fp8kv: the cache type -- 0 = the model dtype, 1 = fp8 e4m3fn, 2 = mxfp4 chunks (struct mxkv)
   // counters: nullptr = merge split contexts in a second kernel; else >= nseq * nkv zeroed
   // arrival counters (left zeroed again) and the last partition to finish merges in place.
   if (nseq == 0) return hipSuccess;
@@ -808,7 +962,20 @@ extern "C" hipError_t lumen_reshape_and_cache(int dtype, const void* k, const vo
   if (D % 8 != 0) return hipErrorInvalidValue;
   const long long total = static_cast<long long>(ntok) * nkv * (D / 8);
   dim3 grid(static_cast<unsigned>((total + 255) / 256)), block(256);
-  if (fp8kv && dtype == lumen::kBF16)
+  // fp8kv: the cache type, as in lumen_paged_attention_decode
+  if (fp8kv == 2 && (D % 32 != 0 || (BS * (D / 2 + D / 32)) % 4 != 0))
+    return hipErrorInvalidValue;
+  if (fp8kv == 2 && dtype == lumen::kBF16)
+    hipLaunchKernelGGL((lumen::cache_write_kernel<lumen::bf16, lumen::mxkv>), grid, block, 0, st,
+                       (const lumen::bf16*)k, (const lumen::bf16*)v, (lumen::mxkv*)kc,
+                       (lumen::mxkv*)vc, slots, ntok, nkv, D, BS, k_stride, v_stride);
+  else if (fp8kv == 2 && dtype == lumen::kF16)
+    hipLaunchKernelGGL((lumen::cache_write_kernel<lumen::fp16, lumen::mxkv>), grid, block, 0, st,
+                       (const lumen::fp16*)k, (const lumen::fp16*)v, (lumen::mxkv*)kc,
+                       (lumen::mxkv*)vc, slots, ntok, nkv, D, BS, k_stride, v_stride);
+  else if (fp8kv == 2)
+    return hipErrorInvalidValue;
+  else if (fp8kv && dtype == lumen::kBF16)
     hipLaunchKernelGGL((lumen::cache_write_kernel<lumen::bf16, lumen::fp8>), grid, block, 0, st,
                        (const lumen::bf16*)k, (const lumen::bf16*)v, (lumen::fp8*)kc,
                        (lumen::fp8*)vc, slots, ntok, nkv, D, BS, k_stride, v_stride);
@@ -837,7 +1004,21 @@ extern "C" hipError_t lumen_rope_cache(int dtype, void* qkv, long long ld, const
   if (D % 16 != 0) return hipErrorInvalidValue;
   const long long n = static_cast<long long>(ntok) * (nh + 2 * nkv) * (D / 16);
   dim3 block(256), grid(static_cast<unsigned>((n + 255) / 256));
-  if (fp8kv && dtype == lumen::kBF16)
+  // fp8kv: the cache type, as in lumen_paged_attention_decode.  mxfp4: head dims whose MX blocks
+  // map onto lane quads / pairs (mx_rope_st)
+  if (fp8kv == 2 && ((D != 32 && D % 64 != 0) || (BS * (D / 2 + D / 32)) % 4 != 0))
+    return hipErrorInvalidValue;
+  if (fp8kv == 2 && dtype == lumen::kBF16)
+    hipLaunchKernelGGL((lumen::rope_cache_kernel<lumen::bf16, lumen::mxkv>), grid, block, 0, st,
+                       (lumen::bf16*)qkv, ld, pos, cos_t, sin_t, (lumen::mxkv*)kc,
+                       (lumen::mxkv*)vc, slots, ntok, nh, nkv, D, BS);
+  else if (fp8kv == 2 && dtype == lumen::kF16)
+    hipLaunchKernelGGL((lumen::rope_cache_kernel<lumen::fp16, lumen::mxkv>), grid, block, 0, st,
+                       (lumen::fp16*)qkv, ld, pos, cos_t, sin_t, (lumen::mxkv*)kc,
+                       (lumen::mxkv*)vc, slots, ntok, nh, nkv, D, BS);
+  else if (fp8kv == 2)
+    return hipErrorInvalidValue;
+  else if (fp8kv && dtype == lumen::kBF16)
     hipLaunchKernelGGL((lumen::rope_cache_kernel<lumen::bf16, lumen::fp8>), grid, block, 0, st,
                        (lumen::bf16*)qkv, ld, pos, cos_t, sin_t, (lumen::fp8*)kc,
                        (lumen::fp8*)vc, slots, ntok, nh, nkv, D, BS);
@@ -873,6 +1054,27 @@ extern "C" hipError_t lumen_kv_dequant(int dtype, const void* kc, const void* vc
   else if (dtype == lumen::kF16)
     hipLaunchKernelGGL(lumen::kv_dequant_kernel<lumen::fp16>, grid, block, 0, st,
                        (const lumen::fp8*)kc, (const lumen::fp8*)vc, (lumen::fp16*)ks,
+                       (lumen::fp16*)vs, tables, tstride, kv_lens, maxb, nkv, BS, D);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+// mxfp4 cache blocks of the prefill sequences -> 16-bit scratch (see kv_dequant_mx_kernel)
+extern "C" hipError_t lumen_kv_dequant_mx(int dtype, const void* kc, const void* vc, void* ks,
+                                          void* vs, const int* tables, int tstride,
+                                          const int* kv_lens, int nseq, int maxb, int nkv, int BS,
+                                          int D, hipStream_t st) {
+  if (nseq == 0 || maxb == 0) return hipSuccess;
+  if (D % 32 != 0 || (BS * (D / 2 + D / 32)) % 4 != 0) return hipErrorInvalidValue;
+  const dim3 grid(nseq, maxb, 2), block(256);
+  if (dtype == lumen::kBF16)
+    hipLaunchKernelGGL(lumen::kv_dequant_mx_kernel<lumen::bf16>, grid, block, 0, st,
+                       (const lumen::mxkv*)kc, (const lumen::mxkv*)vc, (lumen::bf16*)ks,
+                       (lumen::bf16*)vs, tables, tstride, kv_lens, maxb, nkv, BS, D);
+  else if (dtype == lumen::kF16)
+    hipLaunchKernelGGL(lumen::kv_dequant_mx_kernel<lumen::fp16>, grid, block, 0, st,
+                       (const lumen::mxkv*)kc, (const lumen::mxkv*)vc, (lumen::fp16*)ks,
                        (lumen::fp16*)vs, tables, tstride, kv_lens, maxb, nkv, BS, D);
   else
     return hipErrorInvalidValue;

@@ -18,6 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from ._native import native, use_native
+from .quant import MX_BLOCK, Mxfp4Weight, quantize_mxfp4_rows
 
 
 def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
@@ -37,6 +38,89 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     else:
         o = F.scaled_dot_product_attention(q, k, v, is_causal=True, scale=scale)
     return o.transpose(1, 2).reshape(B * S, nh * D)
+
+
+class Mxfp4KV:
+    """One layer's K or V cache in MXFP4 (``--kv-cache-dtype mxfp4``): every head row of D
+    elements is stored as ``quantize_mxfp4_rows(row.view(1, D))`` -- D/2 code bytes (two e2m1 codes
+    a byte, the even element in the low nibble) and D/32 biased E8M0 block-scale bytes, 4.25 bits
+    an element.  Round to nearest, no calibration.
+
+    ``buf`` is the storage the kernels address (``kernels/paged_attention.hip``, struct mxkv):
+    uint8 ``[num_blocks, nkv, block_size * (D/2 + D/32)]``, per (block, head) the block's code rows
+    followed by its scale rows, so both parts live under the same block id and a code row stays
+    16-byte aligned (block_size * D/32 a multiple of 16; the kernels need 4-byte alignment only).
+    ``codes`` / ``scale`` are views of it.  A fresh cache has codes 0 and scales 127:
+    never-written slots read as 0."""
+
+    def __init__(self, num_blocks: int, nkv: int, block_size: int, D: int, device=None):
+        if D % MX_BLOCK:
+            raise ValueError(f"an mxfp4 KV cache needs head_dim % {MX_BLOCK} == 0, got {D}")
+        if (block_size * (D // 2 + D // MX_BLOCK)) % 4:
+            raise ValueError(f"an mxfp4 KV cache needs block_size * head_dim * 17 / 32 to be a "
+                             f"multiple of 4 bytes, got block_size {block_size}, head_dim {D}")
+        self.block_size, self.D = block_size, D
+        self.buf = torch.zeros(num_blocks, nkv, block_size * (D // 2 + D // MX_BLOCK),
+                               dtype=torch.uint8, device=device)
+        self.scale.fill_(127)
+
+    @property
+    def codes(self) -> torch.Tensor:
+        """[num_blocks, nkv, block_size, D/2] uint8 view."""
+        nb, nkv, _ = self.buf.shape
+        n = self.block_size * (self.D // 2)
+        return self.buf[:, :, :n].view(nb, nkv, self.block_size, self.D // 2)
+
+    @property
+    def scale(self) -> torch.Tensor:
+        """[num_blocks, nkv, block_size, D/32] uint8 view."""
+        nb, nkv, _ = self.buf.shape
+        n = self.block_size * (self.D // 2)
+        return self.buf[:, :, n:].view(nb, nkv, self.block_size, self.D // MX_BLOCK)
+
+    @property
+    def shape(self):
+        return torch.Size((self.buf.shape[0], self.buf.shape[1], self.block_size, self.D))
+
+    @property
+    def device(self):
+        return self.buf.device
+
+    @property
+    def is_cuda(self) -> bool:
+        return self.buf.is_cuda
+
+    @property
+    def nbytes(self) -> int:
+        return self.buf.numel()
+
+    def dequant_f32(self, blocks: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[num_blocks, nkv, block_size, D] f32 = f32(code) * 2^(e - 127), exact (every value is
+        also a bf16 number); ``blocks``: only these block ids, in this order."""
+        c, sc = self.codes, self.scale
+        if blocks is not None:
+            c, sc = c[blocks], sc[blocks]
+        w = Mxfp4Weight(c.reshape(-1, self.D // 2), sc.reshape(-1, self.D // MX_BLOCK), self.D,
+                        torch.float32)
+        return w.dequant_f32().view(c.shape[0], c.shape[1], self.block_size, self.D)
+
+    def write(self, rows: torch.Tensor, blk: torch.Tensor, off: torch.Tensor) -> None:
+        """rows [n, nkv, D] -> slots (blk[i], off[i]): the definition (and the CPU path) of what
+        the cache-write kernels store."""
+        n, nkv, D = rows.shape
+        w = quantize_mxfp4_rows(rows.reshape(n * nkv, D))
+        self.codes[blk, :, off] = w.q.view(n, nkv, D // 2)
+        self.scale[blk, :, off] = w.scale.view(n, nkv, D // MX_BLOCK)
+
+
+def _kv_buf(c):
+    """What the native kernels take for a cache: the tensor, or an Mxfp4KV's storage."""
+    return c.buf if isinstance(c, Mxfp4KV) else c
+
+
+def _kv_gather_f32(c, blks):
+    """[len(blks), nkv, bs, D] f32 of the cache blocks ``blks`` (references)."""
+    return c.dequant_f32(blks) if isinstance(c, Mxfp4KV) else c[blks].float()
 
 
 _merge_counters: dict = {}
@@ -93,7 +177,7 @@ def paged_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
         # no per-layer copy of the decode rows' q
         qk = q if (q.stride(2) == 1 and q.stride(1) == D and q.stride(0) % D == 0
                    and q.data_ptr() % 16 == 0) else q.contiguous()
-        native().paged_attention_decode(out, qk, k_cache, v_cache, block_tables,
+        native().paged_attention_decode(out, qk, _kv_buf(k_cache), _kv_buf(v_cache), block_tables,
                                         context_lens, nkv, bs, block_tables.shape[1], scale, tm,
                                         tl, to, partition_size, cnt, one)
         return out
@@ -109,8 +193,8 @@ def paged_decode_ref(q, k_cache, v_cache, block_tables, context_lens, scale):
         L = int(context_lens[i])
         nblk = (L + bs - 1) // bs
         blks = block_tables[i, :nblk].long()
-        kk = k_cache[blks].permute(1, 0, 2, 3).reshape(nkv, nblk * bs, D)[:, :L].float()
-        vv = v_cache[blks].permute(1, 0, 2, 3).reshape(nkv, nblk * bs, D)[:, :L].float()
+        kk = _kv_gather_f32(k_cache, blks).permute(1, 0, 2, 3).reshape(nkv, nblk * bs, D)[:, :L]
+        vv = _kv_gather_f32(v_cache, blks).permute(1, 0, 2, 3).reshape(nkv, nblk * bs, D)[:, :L]
         qq = q[i].float().view(nkv, g, D)
         s = torch.einsum("hgd,hld->hgl", qq, kk) * scale
         p = torch.softmax(s, -1)
@@ -141,7 +225,7 @@ def flash_attention_paged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
               else torch.tensor(list(kv_lens), dtype=torch.int32, device=dev))
         kl = kl.to(torch.int32)
         bt = block_tables.to(torch.int32)
-        if k_cache.dtype == FP8_KV:
+        if isinstance(k_cache, Mxfp4KV) or k_cache.dtype == FP8_KV:
             k_cache, v_cache, bt = _dequant_blocks(k_cache, v_cache, bt, kl, q.dtype)
         native().flash_attn_paged(True, q, k_cache, v_cache, out, cut, kl,
                                   _tiles(cu, 128, dev), bt, nh, nkv, scale)
@@ -156,7 +240,7 @@ _SCRATCH: dict = {}
 
 
 def _dequant_blocks(k_cache, v_cache, bt, kv_lens, dtype):
-    """fp8 cache -> 16-bit scratch holding only the prefill sequences' blocks (block b of
+    """fp8 or mxfp4 cache -> 16-bit scratch holding only the prefill sequences' blocks (block b of
     sequence s at s * maxb + b), plus the identity block table into it: the prefill kernel's
     LDS-DMA staging moves raw 16-bit rows.  The scratch is reused by every layer and grows."""
     P, maxb = bt.shape
@@ -171,7 +255,10 @@ def _dequant_blocks(k_cache, v_cache, bt, kv_lens, dtype):
                torch.arange(n, device=k_cache.device, dtype=torch.int32))
         _SCRATCH[key] = scr
     ks, vs, ident = scr
-    native().kv_dequant(k_cache, v_cache, ks, vs, bt, kv_lens, maxb)
+    if isinstance(k_cache, Mxfp4KV):  # exact in bf16, one rounding in fp16
+        native().kv_dequant_mx(k_cache.buf, v_cache.buf, ks, vs, bt, kv_lens, maxb)
+    else:
+        native().kv_dequant(k_cache, v_cache, ks, vs, bt, kv_lens, maxb)
     return ks, vs, ident[:need].view(P, maxb)
 
 
@@ -188,8 +275,8 @@ def flash_attention_paged_ref(q, k_cache, v_cache, cu_q, kv_lens, block_tables, 
         n, L = b - a, kl[s]
         nblk = (L + bs - 1) // bs
         blks = block_tables[s, :nblk].long()
-        kk = k_cache[blks].permute(1, 0, 2, 3).reshape(nkv, nblk * bs, D)[:, :L].float()
-        vv = v_cache[blks].permute(1, 0, 2, 3).reshape(nkv, nblk * bs, D)[:, :L].float()
+        kk = _kv_gather_f32(k_cache, blks).permute(1, 0, 2, 3).reshape(nkv, nblk * bs, D)[:, :L]
+        vv = _kv_gather_f32(v_cache, blks).permute(1, 0, 2, 3).reshape(nkv, nblk * bs, D)[:, :L]
         qq = q[a:b, :nh * D].float().view(n, nkv, g, D)
         sc = torch.einsum("nhgd,hld->hgnl", qq, kk) * scale
         qpos = torch.arange(L - n, L, device=q.device)[:, None]
@@ -208,14 +295,18 @@ def write_kv_cache(k: torch.Tensor, v: torch.Tensor, k_cache: torch.Tensor,
     if T == 0:
         return
     nb, nkv, bs, D = k_cache.shape
-    if use_native(k_cache):
-        native().reshape_and_cache(k, v, k_cache, v_cache, slot_mapping, nkv, D, bs,
-                                   k.stride(0), v.stride(0))
+    if use_native(_kv_buf(k_cache)):
+        native().reshape_and_cache(k, v, _kv_buf(k_cache), _kv_buf(v_cache), slot_mapping, nkv,
+                                   D, bs, k.stride(0), v.stride(0))
         return
     sm = slot_mapping.long()
     valid = sm >= 0
     sm = sm[valid]
     blk, off = sm // bs, sm % bs
+    if isinstance(k_cache, Mxfp4KV):
+        k_cache.write(k[valid], blk, off)
+        v_cache.write(v[valid], blk, off)
+        return
     k_cache[blk, :, off] = k[valid].to(k_cache.dtype)
     v_cache[blk, :, off] = v[valid].to(v_cache.dtype)
 
@@ -230,9 +321,12 @@ def rope_write_kv(qkv: torch.Tensor, positions: torch.Tensor, nh: int, nkv: int,
     if T == 0:
         return
     nb, nkv_c, bs, Dc = k_cache.shape
-    if use_native(qkv) and D % 16 == 0 and nkv_c == nkv and Dc == D:
-        native().rope_cache_write(qkv, positions.to(torch.int32), cos_t, sin_t, k_cache, v_cache,
-                                  slot_mapping.to(torch.int64), nh, nkv, D, bs)
+    # (over an mxfp4 cache the fused kernel serves the head dims whose MX blocks fall on its lane
+    # quads / pairs; any other goes through rope_inplace + the plain write kernel below)
+    if (use_native(qkv) and D % 16 == 0 and nkv_c == nkv and Dc == D
+            and (not isinstance(k_cache, Mxfp4KV) or D == 32 or D % 64 == 0)):
+        native().rope_cache_write(qkv, positions.to(torch.int32), cos_t, sin_t, _kv_buf(k_cache),
+                                  _kv_buf(v_cache), slot_mapping.to(torch.int64), nh, nkv, D, bs)
         return
     from .rope import rope_inplace
 

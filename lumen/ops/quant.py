@@ -90,6 +90,8 @@ def quantize_fp8_tokens(x: torch.Tensor):
 # (fp4: +-{0, .5, 1, 1.5, 2, 3, 4, 6}).  Round to nearest, no calibration.  The kernels that consume
 # it are in kernels/w4a8_gemm.hip: gfx950's scaled MFMA takes the codes and the block scales as they
 # are stored here; kernels/w4a16_gemm.hip converts them in registers for 16-bit activations.
+# The same definition, applied to every cached K / V head row, is the MXFP4 KV cache
+# (--kv-cache-dtype mxfp4: ops/attention.py Mxfp4KV, kernels/paged_attention.hip).
 MX_BLOCK = 32
 E2M1_MAX = 6.0
 _E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)

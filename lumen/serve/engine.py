@@ -176,9 +176,20 @@ class LLMEngine:
                                     release=own_model and cfg.quantization is not None)
         if cfg.quantization is not None and dev.type == "cuda":
             torch.cuda.empty_cache()  # the released 16-bit projections become KV blocks below
-        if cfg.kv_cache_dtype not in ("auto", "fp8"):
-            raise ValueError(f"kv_cache_dtype must be 'auto' or 'fp8', got {cfg.kv_cache_dtype}")
-        self.kv_dtype = torch.float8_e4m3fn if cfg.kv_cache_dtype == "fp8" else dt
+        if cfg.kv_cache_dtype not in ("auto", "fp8", "mxfp4"):
+            raise ValueError(f"kv_cache_dtype must be 'auto', 'fp8' or 'mxfp4', got "
+                             f"{cfg.kv_cache_dtype}")
+        if cfg.kv_cache_dtype == "mxfp4":
+            # 4.25 bits an element: e2m1 codes + one E8M0 scale byte per 32 elements of a head row
+            # (ops.attention.Mxfp4KV); round to nearest, uncalibrated
+            hd = model.config.head_dim
+            if hd % 32 != 0 or (cfg.block_size * hd * 17 // 32) % 4 != 0:
+                raise ValueError(f"kv_cache_dtype 'mxfp4' needs head_dim % 32 == 0 (MX blocks of 32 "
+                                 f"elements) and block_size * head_dim * 17 / 32 a multiple of 4 "
+                                 f"bytes; this model has head_dim {hd}, block_size {cfg.block_size}")
+            self.kv_dtype = "mxfp4"
+        else:
+            self.kv_dtype = torch.float8_e4m3fn if cfg.kv_cache_dtype == "fp8" else dt
         nb = cfg.num_blocks or self._auto_blocks(self.kv_dtype)
         if self.tp > 1 and dist.is_initialized():
             # one block count for the whole TP group: rank 0 schedules block ids that every
@@ -239,8 +250,8 @@ class LLMEngine:
 
     # --------------------------------------------------------------------------------------
     def _auto_blocks(self, dt) -> int:
-        per_tok = kv_bytes_per_token(self.model_config, torch.tensor([], dtype=dt).element_size(),
-                                     self.tp)
+        esz = 17 / 32 if dt == "mxfp4" else torch.tensor([], dtype=dt).element_size()
+        per_tok = kv_bytes_per_token(self.model_config, esz, self.tp)
         per_block = per_tok * self.cfg.block_size
         if self.device.type == "cuda":
             free, total = torch.cuda.mem_get_info(self.device)

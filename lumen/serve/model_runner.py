@@ -32,7 +32,7 @@ from ..models.config import ModelConfig
 from ..ops._native import native, use_native
 from ..ops.activation import swiglu
 from ..ops.embedding import embedding
-from ..ops.attention import (flash_attention_fresh, flash_attention_paged, paged_decode,
+from ..ops.attention import (Mxfp4KV, flash_attention_fresh, flash_attention_paged, paged_decode,
                              rope_write_kv)
 from ..ops.gemm import linear_nt, swiglu_linear_nt
 from ..ops.norm import rms_norm
@@ -178,15 +178,18 @@ class StepInput:
 
 
 
-def kv_bytes_per_token(cfg: ModelConfig, dtype_bytes: int = 2, tp_size: int = 1) -> int:
-    return 2 * cfg.num_hidden_layers * (cfg.num_key_value_heads // tp_size) * cfg.head_dim * dtype_bytes
+def kv_bytes_per_token(cfg: ModelConfig, dtype_bytes: float = 2, tp_size: int = 1) -> int:
+    """K + V bytes of one token over all layers; ``dtype_bytes`` per element: 2, 1 (fp8) or 17/32
+    (mxfp4: D/2 code bytes + D/32 scale bytes per head row, head_dim % 32 == 0)."""
+    return int(2 * cfg.num_hidden_layers * (cfg.num_key_value_heads // tp_size) * cfg.head_dim
+               * dtype_bytes)
 
 
 class ModelRunner:
     def __init__(self, weights: ServeWeights, num_blocks: int, block_size: int,
                  device: torch.device, max_model_len: int = 4096, tp_group=None,
                  use_graphs: bool = True, max_graph_batch: int = 256, custom_ar=None,
-                 kv_dtype: Optional[torch.dtype] = None):
+                 kv_dtype=None):
         self.w = weights
         self.cfg = weights.cfg
         self.device = device
@@ -200,13 +203,19 @@ class ModelRunner:
         self.q_size, self.kv_size = self.w.nh * D, self.w.nkv * D
         self.max_blocks = (max_model_len + block_size - 1) // block_size
         dt = weights.dtype
-        # KV-cache element type: the model dtype, or fp8 e4m3 (vLLM --kv-cache-dtype fp8: half
-        # the K/V bytes every decode step streams)
+        # KV-cache element type: the model dtype, fp8 e4m3 (vLLM --kv-cache-dtype fp8: half the
+        # K/V bytes every decode step streams), or "mxfp4" (4.25 bits an element, Mxfp4KV holders)
         self.kv_dtype = kv_dtype or dt
-        self.k_cache = [torch.zeros(num_blocks, self.w.nkv, block_size, D, dtype=self.kv_dtype,
-                                    device=device)
-                        for _ in range(cfg.num_hidden_layers)]
-        self.v_cache = [torch.zeros_like(k) for k in self.k_cache]
+        if self.kv_dtype == "mxfp4":
+            self.k_cache = [Mxfp4KV(num_blocks, self.w.nkv, block_size, D, device)
+                            for _ in range(cfg.num_hidden_layers)]
+            self.v_cache = [Mxfp4KV(num_blocks, self.w.nkv, block_size, D, device)
+                            for _ in range(cfg.num_hidden_layers)]
+        else:
+            self.k_cache = [torch.zeros(num_blocks, self.w.nkv, block_size, D,
+                                        dtype=self.kv_dtype, device=device)
+                            for _ in range(cfg.num_hidden_layers)]
+            self.v_cache = [torch.zeros_like(k) for k in self.k_cache]
         self.cos, self.sin = rope_tables(D, max(cfg.max_position_embeddings, max_model_len),
                                          cfg.rope_theta, device)
         self.scale = 1.0 / math.sqrt(D)
