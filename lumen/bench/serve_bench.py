@@ -89,10 +89,18 @@ def bench_engine(a, eng=None) -> dict:
         params["top_p"] = a.top_p
     if getattr(a, "top_k", None) is not None:
         params["top_k"] = a.top_k
+    # per-request sampling state: penalties (counted on the device), min_p, one seed per request
+    if getattr(a, "frequency_penalty", 0.0):
+        params["frequency_penalty"] = a.frequency_penalty
+    if getattr(a, "min_p", 0.0):
+        params["min_p"] = a.min_p
+    per_seed = getattr(a, "seed_per_request", False)
+    new_params = lambda i: SamplingParams(**params, **({"seed": 1000 + i} if per_seed else {}))  # noqa: E731
     # --shared-prefix N: every prompt starts with the same N tokens (a shared system prompt)
     shared = mk(min(getattr(a, "shared_prefix", 0), a.prompt_len))
     prompts = [shared + mk(a.prompt_len - len(shared)) for _ in range(a.num_requests)]
     hit0, q0, pf0 = eng.blocks.hit_tokens, eng.blocks.query_tokens, eng.stats["prefill_tokens"]
+    ov0 = eng.stats["overlapped_steps"]
     seqs = []
     t_start = time.perf_counter()
     if a.request_rate:
@@ -101,14 +109,14 @@ def bench_engine(a, eng=None) -> dict:
         while pending or eng.has_work:
             now = time.perf_counter()
             while pending and now >= next_t:
-                seqs.append(eng.add_request(pending.pop(0), SamplingParams(**params)))
+                seqs.append(eng.add_request(pending.pop(0), new_params(len(seqs))))
                 next_t += rng.expovariate(a.request_rate)
             if eng.has_work:
                 eng.step()
             else:
                 time.sleep(max(0.0, next_t - time.perf_counter()))
     else:
-        seqs = [eng.add_request(p, SamplingParams(**params)) for p in prompts]
+        seqs = [eng.add_request(p, new_params(i)) for i, p in enumerate(prompts)]
         if getattr(a, "trace_steps", False):
             trace = _trace_steps(eng)
         else:
@@ -135,6 +143,10 @@ def bench_engine(a, eng=None) -> dict:
             "kv_blocks": eng.blocks.num_blocks, "preemptions": eng.scheduler.num_preemptions,
             "max_batched_tokens": a.max_batched_tokens, "steps": eng.stats["steps"],
             "async_scheduling": eng.async_sched, "kv_cache_dtype": a.kv_cache_dtype,
+            "overlapped_steps": eng.stats["overlapped_steps"] - ov0,
+            "frequency_penalty": getattr(a, "frequency_penalty", 0.0),
+            "min_p": getattr(a, "min_p", 0.0), "seed_per_request": per_seed,
+            "sampler_state": getattr(eng, "dev_state", None),
             "quantization": getattr(a, "quantization", None),
             "hbm": getattr(eng, "_bench_hbm", None),
             "setup_s": round(getattr(eng, "_bench_setup_s", 0.0), 1),
@@ -277,6 +289,11 @@ def main():
     ap.add_argument("--temperature", type=float, default=0.0)
     ap.add_argument("--top-p", type=float, default=None)
     ap.add_argument("--top-k", type=int, default=None)
+    ap.add_argument("--frequency-penalty", type=float, default=0.0,
+                    help="engine mode: every request carries this frequency penalty")
+    ap.add_argument("--min-p", type=float, default=0.0, help="engine mode: min_p of every request")
+    ap.add_argument("--seed-per-request", action="store_true",
+                    help="engine mode: request i carries seed 1000 + i")
     ap.add_argument("--max-model-len", type=int, default=4096)
     ap.add_argument("--max-num-seqs", type=int, default=256)
     ap.add_argument("--max-batched-tokens", type=int, default=2048)

@@ -120,6 +120,16 @@ hipError_t lumen_reshape_and_cache(int, const void*, const void*, void*, void*, 
 hipError_t lumen_sample(int, const void*, const float*, const float*, const int*,
                         unsigned long long, long long, long long*, float*, float*, int, int,
                         hipStream_t);
+hipError_t lumen_sample_rows(int, const void*, const float*, const float*, const int*,
+                             const long long*, const long long*, const long long*, const float*,
+                             const int*, const int*, const float*, const int*, const float*,
+                             const float*, const float*, int*, int, int, long long*, float*,
+                             float*, int, int, hipStream_t);
+hipError_t lumen_logits_process(int, const void*, const int*, const int*, const float*, const int*,
+                                const float*, const float*, const float*, const int*, int, float*,
+                                int, int, hipStream_t);
+hipError_t lumen_sampler_state_init(int*, const int*, const int*, const int*, const int*, int, int,
+                                    int, hipStream_t);
 hipError_t lumen_flash_attn_paged(int, int, const void*, long long, const void*, const void*, void*,
                                   long long, const int*, const int*, const int*, int, const int*,
                                   int, int, int, int, int, float, hipStream_t);
@@ -1270,6 +1280,119 @@ void sample(const at::Tensor& logits, const at::Tensor& temperature, const at::T
         "sample");
 }
 
+// ---- per-request sampling state (kernels/sampling_rows.hip) --------------------------------
+namespace {
+using OptT = std::optional<at::Tensor>;
+
+void need_vec(const OptT& t, at::ScalarType ty, int64_t n, const char* name) {
+  if (!t) return;
+  if (!t->is_cuda() || !t->is_contiguous() || t->scalar_type() != ty || t->numel() < n)
+    throw std::invalid_argument(std::string("lumen: sampling ") + name +
+                                " must be a contiguous GPU tensor of the documented dtype and size");
+}
+
+// the CSR bias list and the state table of a sample_rows / logits_process call
+void need_row_state(int rows, int V, const OptT& bias_ptr, const OptT& bias_idx,
+                    const OptT& bias_val, const OptT& slot, const OptT& rp, const OptT& fp,
+                    const OptT& pp, const OptT& counts) {
+  need_vec(bias_ptr, at::kInt, rows + 1, "bias_ptr");
+  if (bias_ptr) {
+    if (!bias_idx || !bias_val || bias_idx->numel() != bias_val->numel())
+      throw std::invalid_argument("lumen: sampling bias_ptr needs bias_idx and bias_val of one size");
+    need_vec(bias_idx, at::kInt, 0, "bias_idx");
+    need_vec(bias_val, at::kFloat, 0, "bias_val");
+  }
+  need_vec(slot, at::kInt, rows, "slot");
+  if (counts) {
+    if (counts->dim() != 2 || counts->size(1) != V)
+      throw std::invalid_argument("lumen: sampling counts must be [slots, V]");
+    need_vec(counts, at::kInt, 0, "counts");
+    if (slot && (!rp || !fp || !pp))
+      throw std::invalid_argument("lumen: sampling slot + counts need rp, fp and pp");
+    need_vec(rp, at::kFloat, rows, "rp");
+    need_vec(fp, at::kFloat, rows, "fp");
+    need_vec(pp, at::kFloat, rows, "pp");
+  }
+}
+}  // namespace
+
+void logits_process(const at::Tensor& logits, const OptT& bias_ptr, const OptT& bias_idx,
+                    const OptT& bias_val, const OptT& slot, const OptT& rp, const OptT& fp,
+                    const OptT& pp, const OptT& counts, at::Tensor& out) {
+  need_cuda(logits, "logits");
+  const int V = static_cast<int>(logits.size(-1));
+  const int rows = static_cast<int>(logits.numel() / V);
+  need_row_state(rows, V, bias_ptr, bias_idx, bias_val, slot, rp, fp, pp, counts);
+  need_vec(out, at::kFloat, static_cast<int64_t>(rows) * V, "out");
+  check(lumen_logits_process(dcode(logits), logits.data_ptr(), ptr<int>(bias_ptr),
+                             ptr<int>(bias_idx), ptr<float>(bias_val), ptr<int>(slot),
+                             ptr<float>(rp), ptr<float>(fp), ptr<float>(pp), ptr<int>(counts),
+                             counts ? static_cast<int>(counts->size(0)) : 0,
+                             out.data_ptr<float>(), rows, V, cur_stream()),
+        "logits_process");
+}
+
+// pre: ``logits`` already hold the processed rows (logits_process): bias and penalties are not
+// applied again, the chosen token's count still advances.  V > 32768 goes through an f32
+// scratch of the processed rows and the no-LDS kernel over it.
+void sample_rows(const at::Tensor& logits, const at::Tensor& temperature,
+                 const at::Tensor& top_p, const at::Tensor& top_k, const at::Tensor& seed,
+                 const at::Tensor& offset, const at::Tensor& rngrow, const OptT& min_p,
+                 const OptT& bias_ptr, const OptT& bias_idx, const OptT& bias_val,
+                 const OptT& slot, const OptT& rp, const OptT& fp, const OptT& pp,
+                 const OptT& counts, bool pre, at::Tensor& out_tokens, const OptT& out_logprob,
+                 const OptT& out_tau) {
+  need_cuda(logits, "logits");
+  const int V = static_cast<int>(logits.size(-1));
+  const int rows = static_cast<int>(logits.numel() / V);
+  need_vec(temperature, at::kFloat, rows, "temperature");
+  need_vec(top_p, at::kFloat, rows, "top_p");
+  need_vec(top_k, at::kInt, rows, "top_k");
+  need_vec(seed, at::kLong, rows, "seed");
+  need_vec(offset, at::kLong, rows, "offset");
+  need_vec(rngrow, at::kLong, rows, "rngrow");
+  need_vec(min_p, at::kFloat, rows, "min_p");
+  need_vec(out_tokens, at::kLong, rows, "out_tokens");
+  need_vec(out_logprob, at::kFloat, rows, "out_logprob");
+  need_vec(out_tau, at::kFloat, rows, "out_tau");
+  need_row_state(rows, V, bias_ptr, bias_idx, bias_val, slot, rp, fp, pp, counts);
+  at::Tensor lg = logits;
+  if (V > 32768 && !pre && (bias_ptr || (slot && counts))) {
+    lg = at::empty({rows, V}, logits.options().dtype(at::kFloat));
+    logits_process(logits, bias_ptr, bias_idx, bias_val, slot, rp, fp, pp, counts, lg);
+    pre = true;
+  }
+  check(lumen_sample_rows(
+            dcode(lg), lg.data_ptr(), temperature.data_ptr<float>(), top_p.data_ptr<float>(),
+            top_k.data_ptr<int>(), reinterpret_cast<const long long*>(seed.data_ptr<int64_t>()),
+            reinterpret_cast<const long long*>(offset.data_ptr<int64_t>()),
+            reinterpret_cast<const long long*>(rngrow.data_ptr<int64_t>()), ptr<float>(min_p),
+            ptr<int>(bias_ptr), ptr<int>(bias_idx), ptr<float>(bias_val), ptr<int>(slot),
+            ptr<float>(rp), ptr<float>(fp), ptr<float>(pp), ptr<int>(counts),
+            counts ? static_cast<int>(counts->size(0)) : 0, pre ? 1 : 0,
+            reinterpret_cast<long long*>(out_tokens.data_ptr<int64_t>()), ptr<float>(out_logprob),
+            ptr<float>(out_tau), rows, V, cur_stream()),
+        "sample_rows");
+}
+
+// counts [S, V] int32; slots / n_prompt [n], ptr [n + 1], ids [ptr[n]] int32 (ptr is also given
+// on the host side by ``total`` = ptr[n], which bounds ids)
+void sampler_state_init(at::Tensor& counts, const at::Tensor& slots, const at::Tensor& ptr_t,
+                        const at::Tensor& n_prompt, const at::Tensor& ids, int64_t n) {
+  if (counts.dim() != 2) throw std::invalid_argument("lumen: sampling counts must be [slots, V]");
+  need_vec(counts, at::kInt, 0, "counts");
+  need_vec(slots, at::kInt, n, "slots");
+  need_vec(ptr_t, at::kInt, n + 1, "ptr");
+  need_vec(n_prompt, at::kInt, n, "n_prompt");
+  need_vec(ids, at::kInt, 0, "ids");
+  check(lumen_sampler_state_init(counts.data_ptr<int>(), slots.data_ptr<int>(),
+                                 ptr_t.data_ptr<int>(), n_prompt.data_ptr<int>(),
+                                 ids.data_ptr<int>(), static_cast<int>(n),
+                                 static_cast<int>(counts.size(0)),
+                                 static_cast<int>(counts.size(1)), cur_stream()),
+        "sampler_state_init");
+}
+
 // which: 0 fwd, 1 delta, 2 dK/dV, 3 dQ.  q/k/v/o/dout/dq/dk/dv are (possibly strided) 2-D views
 // [T, cols]: the kernels address head h at column h*128 with the given row strides.
 void flash_attn(int64_t which, bool causal, int64_t mt, const at::Tensor& q, const at::Tensor& k,
@@ -1538,6 +1661,19 @@ PYBIND11_MODULE(_C, m) {
   m.def("sample", &sample, py::arg("logits"), py::arg("temperature"), py::arg("top_p"),
         py::arg("top_k"), py::arg("seed"), py::arg("offset"), py::arg("out_tokens"),
         py::arg("out_logprob") = py::none(), py::arg("out_tau") = py::none());
+  m.def("sample_rows", &sample_rows, py::arg("logits"), py::arg("temperature"), py::arg("top_p"),
+        py::arg("top_k"), py::arg("seed"), py::arg("offset"), py::arg("rngrow"),
+        py::arg("min_p") = py::none(), py::arg("bias_ptr") = py::none(),
+        py::arg("bias_idx") = py::none(), py::arg("bias_val") = py::none(),
+        py::arg("slot") = py::none(), py::arg("rp") = py::none(), py::arg("fp") = py::none(),
+        py::arg("pp") = py::none(), py::arg("counts") = py::none(), py::arg("pre") = false,
+        py::arg("out_tokens"), py::arg("out_logprob") = py::none(),
+        py::arg("out_tau") = py::none());
+  m.def("logits_process", &logits_process, py::arg("logits"), py::arg("bias_ptr") = py::none(),
+        py::arg("bias_idx") = py::none(), py::arg("bias_val") = py::none(),
+        py::arg("slot") = py::none(), py::arg("rp") = py::none(), py::arg("fp") = py::none(),
+        py::arg("pp") = py::none(), py::arg("counts") = py::none(), py::arg("out"));
+  m.def("sampler_state_init", &sampler_state_init);
   m.def("flash_attn", &flash_attn);
   m.def("flash_attn_paged", &flash_attn_paged);
   m.def("flash_attn_ds", &flash_attn_ds);

@@ -4,7 +4,8 @@ The reference declares "vLLM ... OpenAI-compatible API" (README.md:10,16): this 
 surface -- ``GET /v1/models``, ``POST /v1/completions``, ``POST /v1/chat/completions`` (both with
 ``stream: true`` Server-Sent Events ending in ``data: [DONE]``; ``stop`` strings, ``n`` /
 ``best_of``, ``presence_penalty`` / ``frequency_penalty`` and vLLM's ``repetition_penalty``,
-``stop_token_ids``, ``ignore_eos``, ``seed``), ``GET /health`` and a
+``stop_token_ids``, ``ignore_eos``, ``seed``, ``logit_bias``, vLLM's ``min_p`` and
+``min_tokens``), ``GET /health`` and a
 Prometheus-format ``GET /metrics`` (requests, tokens, TTFT / inter-token latency summaries,
 KV-cache usage).  Chat requests use the Llama-2 chat template the reference trains with
 (``<s>[INST] {user} [/INST]``, scripts/prepare_dataset.py:12-25).
@@ -76,6 +77,15 @@ def _quantiles(xs, qs=(0.5, 0.9, 0.99)):
 
 def _params(body: Dict[str, Any], eos: Optional[int]) -> SamplingParams:
     stop_ids = body.get("stop_token_ids") or []
+    bias = body.get("logit_bias")
+    if bias is not None:
+        # OpenAI's JSON shape: {"<token id>": bias}
+        if not isinstance(bias, dict):
+            raise ValueError("logit_bias must be an object of token id -> bias")
+        try:
+            bias = {int(k): float(v) for k, v in bias.items()}
+        except (TypeError, ValueError):
+            raise ValueError("logit_bias keys must be token ids and its values numbers")
     return SamplingParams(max_tokens=int(body.get("max_tokens") or 16),
                           temperature=float(body.get("temperature", 1.0)),
                           top_p=float(body.get("top_p", 1.0)), top_k=int(body.get("top_k", 0) or 0),
@@ -83,7 +93,9 @@ def _params(body: Dict[str, Any], eos: Optional[int]) -> SamplingParams:
                           seed=body.get("seed"),
                           presence_penalty=float(body.get("presence_penalty") or 0.0),
                           frequency_penalty=float(body.get("frequency_penalty") or 0.0),
-                          repetition_penalty=float(body.get("repetition_penalty") or 1.0))
+                          repetition_penalty=float(body.get("repetition_penalty") or 1.0),
+                          min_p=float(body.get("min_p") or 0.0), logit_bias=bias or None,
+                          min_tokens=int(body.get("min_tokens") or 0))
 
 
 def _logprob_request(body: Dict[str, Any], chat: bool, params: SamplingParams) -> bool:

@@ -23,7 +23,9 @@ import torch.distributed as dist
 
 from ..models import build_model, get_config
 from .block_manager import BlockManager
-from .model_runner import ModelRunner, ServeWeights, StepInput, kv_bytes_per_token
+from .model_runner import (ModelRunner, ServeWeights, StepInput, kv_bytes_per_token,
+                           process_logits_ref, sample_rows_ref)
+from .sampler_state import RowParams, SamplerState, bias_csr, counts_from_ids
 from .scheduler import Batch, Scheduler, SchedulerConfig
 from .sequence import SamplingParams, Sequence, Status
 
@@ -244,6 +246,15 @@ class LLMEngine:
         self.tokenizer = tokenizer
         self.eos_id = getattr(tokenizer, "eos_token_id", self.model_config.eos_token_id)
         self.step_count = 0
+        # penalty counts of the running sequences on the device (allocated at the first request
+        # with a penalty); LUMEN_SAMPLER_STATE=0 forces the host path (apply_penalties) for A/B
+        # runs.  Rank 0 only: TP workers never sample.
+        from ..ops._native import native
+        self.dev_state = (dev.type == "cuda" and native() is not None
+                          and os.environ.get("LUMEN_DISABLE_NATIVE", "0") != "1"
+                          and os.environ.get("LUMEN_SAMPLER_STATE", "1") != "0")
+        self.sampler_state = SamplerState(cfg.max_num_seqs, self.model_config.vocab_size, dev)
+        self.scheduler.on_release = self.sampler_state.release
         self.stats = {"prefill_tokens": 0, "decode_tokens": 0, "steps": 0, "requests": 0,
                       "finished": 0, "overlapped_steps": 0, "spec_proposed": 0,
                       "spec_accepted": 0, "spec_steps": 0}
@@ -287,6 +298,14 @@ class LLMEngine:
             params.max_tokens = budget
         if params.prompt_logprobs is not None and self.tp > 1:
             raise ValueError("prompt_logprobs is served at tensor-parallel size 1 only")
+        if params.min_tokens > params.max_tokens:
+            params.min_tokens = params.max_tokens
+        if params.logit_bias:
+            V = self.model_config.vocab_size
+            bad = [t for t in params.logit_bias if not 0 <= t < V]
+            if bad:
+                raise ValueError(f"logit_bias token id {bad[0]} is outside the vocabulary "
+                                 f"(0..{V - 1})")
         seq = Sequence(ids, params, request_id or uuid.uuid4().hex)
         if lora:
             if self.runner.lora is None or lora not in self.lora_names:
@@ -381,14 +400,15 @@ class LLMEngine:
         if batch.kind == "verify":
             # speculative verification: every row of a drafted chunk is scored
             done_rows = list(range(Tp))
-            ps = [s.params for s, c in batch.prefills for _ in range(c)]
-            ps += [s.params for s in batch.decodes]
+            rseqs = [s for s, c in batch.prefills for _ in range(c)] + batch.decodes
+            ps = [s.params for s in rseqs]
         else:
             n_done = len(batch.completing())
             done_rows = [cu[i + 1] - 1 for i, (s, c) in enumerate(batch.prefills)
                          if s.num_cached + c == s.length]
             assert len(done_rows) == n_done
-            ps = [s.params for s in batch.sampled]
+            rseqs = batch.sampled
+            ps = [s.params for s in rseqs]
         rows = np.concatenate([np.asarray(done_rows, dtype=np.int64),
                                np.arange(Tp, T, dtype=np.int64)])
         extra.append(rows)
@@ -400,6 +420,10 @@ class LLMEngine:
             extra += [np.fromiter((p.temperature for p in ps), np.float64, R).view(np.int64),
                       np.fromiter((p.top_p for p in ps), np.float64, R).view(np.int64),
                       np.fromiter((p.top_k for p in ps), np.int64, R)]
+        rowp = None
+        if R and any(p.row_features or (self.dev_state and p.has_penalties) for p in ps):
+            rowp = self._row_params(batch, rseqs, ps, Tp)
+            extra += rowp["pack"]
         if prows:
             extra.append(np.asarray(prows, dtype=np.int64))
         if use_lora:
@@ -435,6 +459,8 @@ class LLMEngine:
             inp.top_ps = dev[o + R:o + 2 * R].view(torch.float64).float()
             inp.top_ks = dev[o + 2 * R:o + 3 * R].int()
             o += 3 * R
+        if rowp is not None:
+            o = self._unpack_row_params(inp, rowp, dev, o, R)
         if prows:
             inp.extra_rows = dev[o:o + len(prows)]
             inp.prompt_meta = pmeta
@@ -442,6 +468,158 @@ class LLMEngine:
         if use_lora:
             inp.lora_ids = dev[o:o + T].int()
         return inp
+
+    def _row_bias(self, s: Sequence, k: int = 0):
+        """(ids, values) of the row's logit_bias entries, with min_tokens lowered to -inf entries
+        for EOS and the stop ids while the sequence (its in-flight tokens and ``k`` more
+        counted) is below min_tokens; None when it has neither."""
+        p = s.params
+        ban = p.min_tokens > 0 and s.num_generated + k < p.min_tokens
+        if p.logit_bias is None and not ban:
+            return None
+        if not ban:
+            if s.bias_np is None:
+                s.bias_np = (np.fromiter(p.logit_bias.keys(), np.int64, len(p.logit_bias)),
+                             np.fromiter(p.logit_bias.values(), np.float64, len(p.logit_bias)))
+            return s.bias_np
+        V = self.model_config.vocab_size
+        d = dict(p.logit_bias or {})
+        stops = list(p.stop_token_ids)
+        if not p.ignore_eos and self.eos_id is not None:
+            stops.append(self.eos_id)
+        for t in stops:
+            if 0 <= t < V:
+                d[int(t)] = -float("inf")
+        return (np.fromiter(d.keys(), np.int64, len(d)), np.fromiter(d.values(), np.float64, len(d)))
+
+    def _row_params(self, batch: Batch, rseqs: List[Sequence], ps, Tp: int) -> dict:
+        """Host arrays of the per-row sampler arguments of this step (they ride in the packed
+        step copy), and the state slots of the sequences that are sampled for the first time.
+        A request with a seed draws from (its seed, tokens generated so far, 0): the same
+        tokens whatever else runs; one without from (engine seed, step, its row)."""
+        R = len(rseqs)
+        verify = batch.kind == "verify"
+        # rows of a drafted chunk (verify steps): greedy, no bias, no state -- _propose drafts
+        # only such sequences; k = the row's position in its chunk
+        kpos = np.zeros(R, dtype=np.int64)
+        if verify and Tp:
+            kpos[:Tp] = np.concatenate([np.arange(c) for _, c in batch.prefills])
+        eseed = int(self.cfg.seed) & 0x7FFFFFFFFFFFFFFF
+        seeded = np.fromiter((p.seed is not None for p in ps), np.bool_, R)
+        seed = np.fromiter((eseed if p.seed is None else int(p.seed) & 0x7FFFFFFFFFFFFFFF
+                            for p in ps), np.int64, R)
+        gen = np.fromiter((s.num_generated for s in rseqs), np.int64, R) + kpos
+        offset = np.where(seeded, gen, self.step_count)
+        rngrow = np.where(seeded, 0, np.arange(R, dtype=np.int64))
+        new = []
+        if self.dev_state:
+            st = self.sampler_state
+            for i, s in enumerate(rseqs):
+                if ps[i].has_penalties and s.state_slot < 0 and not (verify and i < Tp):
+                    s.state_slot = st.acquire()
+                    new.append(s)
+        slot = np.fromiter((-1 if (verify and i < Tp) else s.state_slot
+                            for i, s in enumerate(rseqs)), np.int64, R)
+        f4 = np.concatenate([np.fromiter((p.min_p for p in ps), np.float64, R),
+                             np.fromiter((p.repetition_penalty for p in ps), np.float64, R),
+                             np.fromiter((p.frequency_penalty for p in ps), np.float64, R),
+                             np.fromiter((p.presence_penalty for p in ps), np.float64, R)])
+        bias = [None if (verify and i < Tp) or not (ps[i].logit_bias or ps[i].min_tokens)
+                else self._row_bias(s, int(kpos[i])) for i, s in enumerate(rseqs)]
+        bptr, bidx, bval = bias_csr(bias)
+        nb = len(bidx)
+        pack = [seed, offset, rngrow, f4.view(np.int64), slot]
+        if nb:
+            pack += [bptr, bidx, bval.view(np.int64)]
+        n_ids = 0
+        if new:
+            lens = np.fromiter((len(s.prompt_ids) + len(s.output_ids) for s in new), np.int64,
+                               len(new))
+            iptr = np.zeros(len(new) + 1, dtype=np.int64)
+            np.cumsum(lens, out=iptr[1:])
+            n_ids = int(iptr[-1])
+            pack += [np.fromiter((s.state_slot for s in new), np.int64, len(new)), iptr,
+                     np.fromiter((len(s.prompt_ids) for s in new), np.int64, len(new))]
+            pack += [np.asarray(s.prompt_ids + s.output_ids, dtype=np.int64) for s in new]
+        host = {"seeds": [p.seed for p in ps], "offsets": offset, "bias": bias, "seqs": rseqs,
+                "min_p": f4[:R], "rp": f4[R:2 * R], "fp": f4[2 * R:3 * R], "pp": f4[3 * R:]}
+        return {"pack": pack, "nb": nb, "new": len(new), "n_ids": n_ids, "host": host}
+
+    @staticmethod
+    def _unpack_row_params(inp: StepInput, rowp: dict, dev: torch.Tensor, o: int, R: int) -> int:
+        """The device views of ``_row_params``'s arrays in the packed copy ``dev`` from ``o``."""
+        seed, offset, rngrow = dev[o:o + R], dev[o + R:o + 2 * R], dev[o + 2 * R:o + 3 * R]
+        o += 3 * R
+        f4 = dev[o:o + 4 * R].view(torch.float64).float()
+        o += 4 * R
+        nb, n, n_ids = rowp["nb"], rowp["new"], rowp["n_ids"]
+        ni = R + ((R + 1 + nb) if nb else 0)
+        ints = dev[o:o + ni].int()    # slot | bias_ptr | bias_idx in one conversion
+        o += ni
+        sp = RowParams(seed, offset, rngrow, f4[:R], ints[:R], f4[R:2 * R], f4[2 * R:3 * R],
+                       f4[3 * R:], host=rowp["host"])
+        if nb:
+            sp.bias_ptr, sp.bias_idx = ints[R:2 * R + 1], ints[2 * R + 1:]
+            sp.bias_val = dev[o:o + nb].view(torch.float64).float()
+            o += nb
+        if n:
+            init = dev[o:o + 3 * n + 1 + n_ids].int()
+            o += 3 * n + 1 + n_ids
+            sp.host["init"] = (init[:n], init[n:2 * n + 1], init[2 * n + 1:3 * n + 1],
+                               init[3 * n + 1:])
+        inp.samp = sp
+        return o
+
+    def _sample(self, inp: StepInput, logits: torch.Tensor, rseqs: List[Sequence],
+                want_x: bool = False):
+        """Sample the step's rows (``rseqs``: the sequence of each row).  Returns (tokens,
+        logprobs, the logits the tokens were drawn from).  Steps that use no per-request seed,
+        min_p, logit_bias, min_tokens or device-side penalty take the plain ``sample`` entry
+        with today's arguments; the others the per-row entry (kernels/sampling_rows.hip), or
+        the torch references where there is no native extension."""
+        ps = [s.params for s in rseqs]
+        sp = inp.samp
+        host_pen = not self.dev_state and any(p.has_penalties for p in ps)
+        if sp is None:
+            if host_pen:
+                logits = apply_penalties(logits, rseqs)
+            seed = self.cfg.seed if ps[0].seed is None else ps[0].seed
+            t, lp = self.runner.sample(logits, inp.temps, inp.top_ps, inp.top_ks, seed,
+                                       self.step_count, want_logprobs=True)
+            return t, lp, logits
+        h = sp.host
+        if not (logits.is_cuda and self._native_rows(logits)):
+            counts = None
+            if host_pen:
+                V = logits.shape[1]
+                counts = torch.stack([
+                    counts_from_ids(s.prompt_ids, s.output_ids, V) if s.params.has_penalties
+                    else torch.zeros(V, dtype=torch.int64) for s in rseqs])
+            x = process_logits_ref(logits, counts, h["rp"], h["fp"], h["pp"], bias=h["bias"])
+            t, lp = sample_rows_ref(x, inp.temps, inp.top_ps, inp.top_ks, h["min_p"],
+                                    h["seeds"], h["offsets"], self.cfg.seed, self.step_count)
+            return t, lp, x
+        counts = None
+        if "init" in h:
+            self.sampler_state.init_slots(*h.pop("init"))
+        if self.dev_state and self.sampler_state.allocated:
+            counts = self.sampler_state.counts
+        pre = False
+        if host_pen:
+            # LUMEN_SAMPLER_STATE=0: the bias on the device, then the host-side penalties
+            logits = apply_penalties(self.runner.logits_process(logits, sp), rseqs)
+            pre = True
+        elif want_x:
+            logits = self.runner.logits_process(logits, sp, counts)
+            pre = True
+        t, lp = self.runner.sample_rows(logits, inp.temps, inp.top_ps, inp.top_ks, sp, counts,
+                                        pre=pre, want_logprobs=True)
+        return t, lp, logits
+
+    @staticmethod
+    def _native_rows(logits: torch.Tensor) -> bool:
+        from ..ops._native import use_native
+        return use_native(logits)
 
     def _to_device(self, host: "np.ndarray") -> torch.Tensor:
         t = torch.from_numpy(host)
@@ -512,12 +690,13 @@ class LLMEngine:
             return None
         return Batch("mixed" if pre else "decode", pre, dec)
 
-    @staticmethod
-    def _needs_host_tokens(batch: Batch) -> bool:
-        """Prefill rows re-reading generated tokens (preemption recompute) and penalties need
-        the in-flight step's token VALUES on the host."""
+    def _needs_host_tokens(self, batch: Batch) -> bool:
+        """Prefill rows re-reading generated tokens (preemption recompute) need the in-flight
+        step's token VALUES on the host; so do penalties on the host path (no native extension,
+        or LUMEN_SAMPLER_STATE=0) -- with the device state the sampler keeps the counts."""
         return (any(s.has_pending for s, _ in batch.prefills)
-                or any(s.params.has_penalties for s in batch.sampled))
+                or (not self.dev_state
+                    and any(s.params.has_penalties for s in batch.sampled)))
 
     def _launch(self, batch: Batch) -> None:
         inp = self._build_input(batch)
@@ -532,12 +711,7 @@ class LLMEngine:
         self.stats["decode_tokens"] += len(batch.decodes)
         rec = {"sampled": [], "row": {}, "toks": None}
         if sampled:
-            ps = [s.params for s in sampled]
-            seed = self.cfg.seed if ps[0].seed is None else ps[0].seed
-            if any(p.has_penalties for p in ps):
-                logits = apply_penalties(logits, sampled)
-            t, lp = self.runner.sample(logits, inp.temps, inp.top_ps, inp.top_ks, seed,
-                                       self.step_count, want_logprobs=True)
+            t, lp, _ = self._sample(inp, logits, sampled)
             R = t.shape[0]
             th = torch.empty(R, dtype=torch.long, pin_memory=self.device.type == "cuda")
             th.copy_(t, non_blocking=True)
@@ -605,12 +779,9 @@ class LLMEngine:
         self.stats["decode_tokens"] += len(batch.decodes)
         toks, lps = [], []
         if sampled:
-            ps = [s.params for s in sampled]
-            seed = self.cfg.seed if ps[0].seed is None else ps[0].seed
-            if any(p.has_penalties for p in ps):
-                logits = apply_penalties(logits, sampled)
-            t, lp = self.runner.sample(logits, inp.temps, inp.top_ps, inp.top_ks, seed,
-                                       self.step_count, want_logprobs=True)
+            # alternatives (_extras) are read from the processed logits the token is drawn from
+            t, lp, logits = self._sample(inp, logits, sampled,
+                                         want_x=any(s.params.top_logprobs for s in sampled))
             toks = t.tolist()
             lps = lp.tolist() if lp is not None else [None] * len(toks)
         tops = self._extras(inp, logits, sampled)
@@ -679,6 +850,8 @@ class LLMEngine:
             p = s.params
             if p.temperature > 0 or p.has_penalties or p.wants_extras:
                 continue
+            if p.logit_bias or s.num_generated < p.min_tokens:
+                continue                      # drafted rows carry no bias and no bans
             if s.spec_wait > 0:
                 s.spec_wait -= 1
                 continue
@@ -725,13 +898,8 @@ class LLMEngine:
             self._broadcast(inp)
         logits = self.runner.execute(inp)
         # drafted rows are greedy (argmax); the undrafted decode rows keep their own sampling
-        if any(s.params.has_penalties for s in vb.decodes):
-            logits = apply_penalties(logits, [s for s, c in vb.prefills for _ in range(c)]
-                                     + vb.decodes)
-        p0 = vb.seqs[0].params
-        t, lp = self.runner.sample(logits, inp.temps, inp.top_ps, inp.top_ks,
-                                   self.cfg.seed if p0.seed is None else p0.seed,
-                                   self.step_count, want_logprobs=True)
+        t, lp, _ = self._sample(inp, logits,
+                                [s for s, c in vb.prefills for _ in range(c)] + vb.decodes)
         amv = t.tolist()
         lpv = lp.tolist() if lp is not None else [None] * len(amv)
         self.runner.check_collectives()

@@ -170,6 +170,9 @@ class StepInput:
     top_ks: Optional[torch.Tensor] = None        # [R] int32
     extra_rows: Optional[torch.Tensor] = None    # prompt-logprob rows (TP = 1), int64 [E]
     prompt_meta: Optional[list] = None           # host: (seq, first scored token, count, row)
+    # per-row sampler arguments (sampler_state.RowParams) of a step that uses per-request seeds,
+    # min_p, logit_bias, min_tokens or device-side penalties; None: the plain ``sample`` entry
+    samp: Optional[object] = None
 
     @property
     def num_prefill_rows(self) -> int:
@@ -529,6 +532,35 @@ class ModelRunner:
             return out, lp
         return sample_ref(logits, t, p, k, seed, offset)
 
+    @torch.no_grad()
+    def logits_process(self, logits: torch.Tensor, sp, counts: Optional[torch.Tensor] = None):
+        """The processed f32 logits of the sampled rows (logit_bias, then the penalties from
+        ``counts``): what ``sample_rows`` draws from, materialised."""
+        out = torch.empty(logits.shape, dtype=torch.float32, device=logits.device)
+        st = counts is not None
+        native().logits_process(logits.contiguous(), sp.bias_ptr, sp.bias_idx, sp.bias_val,
+                                sp.slot if st else None, sp.rp if st else None,
+                                sp.fp if st else None, sp.pp if st else None, counts, out)
+        return out
+
+    @torch.no_grad()
+    def sample_rows(self, logits: torch.Tensor, temps, top_ps, top_ks, sp,
+                    counts: Optional[torch.Tensor] = None, pre: bool = False,
+                    want_logprobs: bool = True):
+        """The per-row sampler entry (kernels/sampling_rows.hip): ``sp`` is a RowParams of device
+        tensors.  ``pre``: the logits are ``logits_process`` output already (the sampled tokens'
+        counts still advance)."""
+        R = logits.shape[0]
+        dev = logits.device
+        out = torch.empty(R, dtype=torch.long, device=dev)
+        lp = torch.empty(R, dtype=torch.float32, device=dev) if want_logprobs else None
+        st = counts is not None
+        native().sample_rows(logits.contiguous(), temps, top_ps, top_ks, sp.seed, sp.offset,
+                             sp.rngrow, sp.min_p, sp.bias_ptr, sp.bias_idx, sp.bias_val,
+                             sp.slot if st else None, sp.rp if st else None,
+                             sp.fp if st else None, sp.pp if st else None, counts, pre, out, lp)
+        return out, lp
+
 
 def topk_topp_keep(zs: torch.Tensor, k: int, p: float) -> torch.Tensor:
     """The kept set of vLLM 0.6.0's ``_apply_top_k_top_p`` for one row of scaled logits: top-k
@@ -567,6 +599,75 @@ def sample_ref(logits, temps, top_ps, top_ks, seed, offset):
             probs = torch.softmax(zs, -1)
             pr = torch.where(keep, probs, torch.zeros_like(probs))
             tok = int(torch.multinomial(pr / pr.sum(), 1, generator=g))
+        out[i] = tok
+        lps[i] = torch.log_softmax(zs, -1)[tok]
+    return out, lps
+
+
+def process_logits_ref(logits, counts=None, rp=None, fp=None, pp=None, bias=None):
+    """Torch reference of steps 1-3 of the per-row sampler (kernels/sampling_rows.hip), in
+    ``logits.float()`` precision (pass f64 logits for an f64 reference): ``bias`` is a list of
+    (idx, val) pairs per row or None; ``counts`` [R, V] integer rows (bit 31 = in the prompt,
+    bits 0..30 = times generated; an all-zero row = no state).  logit_bias first, then the
+    repetition penalty on the biased logit's sign, then frequency / presence."""
+    x = logits.clone() if logits.dtype == torch.float64 else logits.float().clone()
+    R, V = x.shape
+    if bias is not None:
+        for i, e in enumerate(bias):
+            if e is None:
+                continue
+            idx = torch.as_tensor(e[0], dtype=torch.long)
+            val = torch.as_tensor(e[1], dtype=x.dtype)
+            ok = (idx >= 0) & (idx < V)
+            x[i].index_add_(0, idx[ok].to(x.device), val[ok].to(x.device))
+    if counts is not None:
+        c = counts.to(x.device).long()
+        n = (c & 0x7FFFFFFF).to(x.dtype)
+        rp = torch.as_tensor(rp, dtype=x.dtype, device=x.device)[:, None]
+        fp = torch.as_tensor(fp, dtype=x.dtype, device=x.device)[:, None]
+        pp = torch.as_tensor(pp, dtype=x.dtype, device=x.device)[:, None]
+        seen = (c != 0) & (rp != 1.0)
+        x = torch.where(seen, torch.where(x > 0, x / rp, x * rp), x)
+        pen = fp * n + pp * (n > 0).to(x.dtype)
+        x = torch.where(c != 0, x - pen, x)
+    return x
+
+
+def min_p_keep(zs: torch.Tensor, min_p: float) -> torch.Tensor:
+    """vLLM's min_p on one row of scaled logits: p_j >= min_p * p_max, i.e.
+    z_j >= max(z) + ln(min_p); the ratio is the same before and after top-k / top-p."""
+    if min_p <= 0.0:
+        return torch.ones_like(zs, dtype=torch.bool)
+    if min_p >= 1.0:
+        return zs >= zs.max()
+    return zs >= zs.max() + math.log(min_p)
+
+
+def sample_rows_ref(x, temps, top_ps, top_ks, min_ps, seeds, offsets, seed, offset):
+    """Torch sampler over processed logits ``x`` (CPU path of the per-row entry): a row with
+    ``seeds[i]`` set draws from its own generator seeded from (seed, offset) of that row -- the
+    same token whatever else is in the batch; the other rows share the step's generator."""
+    R, V = x.shape
+    g = torch.Generator(device=x.device).manual_seed((seed * 1000003 + offset) & 0x7FFFFFFF)
+    out = torch.empty(R, dtype=torch.long, device=x.device)
+    lps = torch.empty(R, dtype=torch.float32, device=x.device)
+    for i in range(R):
+        z = x[i].float()
+        T = float(temps[i])
+        if T <= 0:
+            tok = int(z.argmax())
+            zs = z
+        else:
+            zs = z / T
+            keep = topk_topp_keep(zs, int(top_ks[i]), float(top_ps[i]))
+            keep &= min_p_keep(zs, float(min_ps[i]))
+            probs = torch.softmax(zs, -1)
+            pr = torch.where(keep, probs, torch.zeros_like(probs))
+            gi = g
+            if seeds[i] is not None:
+                gi = torch.Generator(device=x.device).manual_seed(
+                    (int(seeds[i]) * 1000003 + int(offsets[i])) & 0x7FFFFFFF)
+            tok = int(torch.multinomial(pr / pr.sum(), 1, generator=gi))
         out[i] = tok
         lps[i] = torch.log_softmax(zs, -1)[tok]
     return out, lps

@@ -90,6 +90,9 @@ class Scheduler:
         self.waiting: Deque[Sequence] = deque()
         self.running: List[Sequence] = []
         self.num_preemptions = 0
+        # called with every sequence whose blocks are released (finish, abort, preemption): the
+        # engine returns the sequence's sampler-state slot there
+        self.on_release = None
 
     def add(self, seq: Sequence) -> None:
         if seq.length > self.cfg.max_model_len:
@@ -104,6 +107,8 @@ class Scheduler:
                     q.remove(s)
                     s.status, s.finish_reason = Status.FINISHED, "abort"
                     self.blocks.free_seq(s.seq_id)
+                    if self.on_release is not None:
+                        self.on_release(s)
 
     @property
     def has_work(self) -> bool:
@@ -227,6 +232,8 @@ class Scheduler:
         whose K/V launched steps wrote stay cached (a recomputed or follow-up prompt hits them)."""
         self.blocks.free_seq(s.seq_id, s.all_ids, min(s.num_cached, len(s.all_ids)),
                              s.lora_slot)
+        if self.on_release is not None:
+            self.on_release(s)
 
     def _preempt(self, s: Sequence) -> None:
         self.running.remove(s)

@@ -5,7 +5,7 @@ import enum
 import itertools
 import time
 from dataclasses import dataclass, field
-from typing import List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 
 @dataclass
@@ -30,6 +30,12 @@ class SamplingParams:
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     repetition_penalty: float = 1.0
+    # vLLM's min_p (keep tokens with p >= min_p * p_max, after top-k / top-p; 0 = off), OpenAI's
+    # logit_bias ({token id: bias in [-100, 100]}, added to the logit before the penalties) and
+    # vLLM's min_tokens (EOS and the stop ids cannot be sampled before that many tokens)
+    min_p: float = 0.0
+    logit_bias: Optional[Dict[int, float]] = None
+    min_tokens: int = 0
 
     @property
     def has_penalties(self) -> bool:
@@ -51,6 +57,27 @@ class SamplingParams:
             raise ValueError("top_logprobs must be in [0, 20]")
         if self.prompt_logprobs is not None and not 0 <= self.prompt_logprobs <= 20:
             raise ValueError("prompt_logprobs must be in [0, 20]")
+        if not 0.0 <= self.min_p <= 1.0:
+            raise ValueError("min_p must be in [0, 1]")
+        if not 0 <= self.min_tokens <= self.max_tokens:
+            raise ValueError("min_tokens must be in [0, max_tokens]")
+        if self.logit_bias is not None:
+            if not isinstance(self.logit_bias, dict) or len(self.logit_bias) > 300:
+                raise ValueError("logit_bias must be a {token id: bias} map of at most 300 entries")
+            try:
+                bias = {int(k): float(v) for k, v in self.logit_bias.items()}
+            except (TypeError, ValueError):
+                raise ValueError("logit_bias keys must be token ids and its values numbers")
+            if any(k < 0 for k in bias) or not all(-100.0 <= v <= 100.0 for v in bias.values()):
+                raise ValueError("logit_bias ids must be >= 0 and its values in [-100, 100]")
+            self.logit_bias = bias or None
+
+    @property
+    def row_features(self) -> bool:
+        """Anything the per-row sampler entry serves beyond temperature / top-k / top-p (the
+        penalties count only where the engine keeps their state on the device)."""
+        return ((self.seed is not None and self.temperature > 0) or self.min_p > 0.0
+                or self.logit_bias is not None or self.min_tokens > 0)
 
     @property
     def wants_extras(self) -> bool:
@@ -101,6 +128,8 @@ class Sequence:
     # prompt lookup: n-gram -> position after its latest occurrence, over all_ids[:ngram_upto]
     ngram_idx: dict = field(default_factory=dict, repr=False)
     ngram_upto: int = 0
+    state_slot: int = -1         # row of the device sampler state (penalty counts); -1: none
+    bias_np: Optional[tuple] = field(default=None, repr=False)   # logit_bias as (ids, values)
 
     @property
     def all_ids(self) -> List[int]:
@@ -145,6 +174,11 @@ class Sequence:
             self.status, self.finish_reason = Status.FINISHED, "stop"
         elif len(self.output_ids) >= p.max_tokens:
             self.status, self.finish_reason = Status.FINISHED, "length"
+
+    @property
+    def num_generated(self) -> int:
+        """Tokens generated so far, the in-flight ones included."""
+        return len(self.output_ids) + self.n_pending
 
     @property
     def has_pending(self) -> bool:
