@@ -1,9 +1,9 @@
 // Python binding for lumen's native ops (built into lumen/_C*.so by lumen/csrc/build.py).
 //
 // Every function here only checks arguments, picks the dtype code and the current HIP stream,
-// and calls an `extern "C"` launcher from kernels/*.hip.  Allocation and shape logic live in
-// lumen/ops/*.py so this translation unit (the only one that includes the heavy torch headers)
-// rarely changes.
+// and calls a launcher from kernels/*.hip, declared in kernels/api.h.  Allocation and shape logic
+// live in lumen/ops/*.py so this translation unit (the only one that includes the heavy torch
+// headers) rarely changes.
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
@@ -14,156 +14,8 @@
 #include <string>
 #include <vector>
 
-extern "C" {
-hipError_t lumen_rmsnorm_fwd(int, const void*, const void*, const void*, void*, void*, float*, int,
-                             int, float, hipStream_t);
-hipError_t lumen_rmsnorm_bwd(int, const void*, const void*, const void*, const float*, const void*,
-                             void*, float*, int, int, hipStream_t);
-hipError_t lumen_qkv_rope(int, int, void*, void*, void*, void*, const int*, const float*,
-                          const float*, int, int, int, int, int, hipStream_t);
-hipError_t lumen_rope_inplace(int, void*, const int*, const float*, const float*, int, int, int,
-                              int, hipStream_t);
-hipError_t lumen_swiglu(int, int, const void*, const void*, void*, int, int, int, int, hipStream_t);
-hipError_t lumen_scale_dev(int, void*, long long, const float*, const float*, hipStream_t);
-hipError_t lumen_cross_entropy(int, void*, const int64_t*, float*, float*, int, int, int, float,
-                               int, const float*, hipStream_t);
-hipError_t lumen_grad_norm_sq(int, const void*, long long, float*, hipStream_t);
-hipError_t lumen_adamw(float*, int, const void*, float*, float*, int, void*, long long, float, float,
-                       float, float, float, float, float, float, const float*, float, float*,
-                       const double*, hipStream_t);
-hipError_t lumen_lora_gemm(int, int, int, const void*, const void*, void*, long long, long long,
-                           long long, long long, float, int, unsigned long long, unsigned int, float,
-                           long long, int, const long long*, const long long*, const long long*,
-                           const int*, const int*, const int*, hipStream_t);
-hipError_t lumen_lora2(int, int, int, const void*, long long, const float*, long long, void*,
-                       long long, long long, float, int, int, int, unsigned long long, unsigned int,
-                       float, long long, long long, int, const long long*, const long long*,
-                       const long long*, const int*, const float*, const float*, const int*, int,
-                       hipStream_t);
-hipError_t lumen_rmsnorm_fwd_ld(int, const void*, const void*, const void*, void*, void*, float*,
-                                int, int, float, long long, hipStream_t);
-hipError_t lumen_lora3_z_tail(int, const float*, int, void*, long long, int, int, int, hipStream_t);
-hipError_t lumen_lora3_w_tail_batch(int, const long long*, int, long long, hipStream_t);
-hipError_t lumen_lora3_w_tail(int, void*, long long, int, const float*, int, int, const long long*,
-                              const long long*, const int*, const int*, float, hipStream_t);
-hipError_t lumen_lora3_dxa(int, const void*, long long, void*, long long, const float*, const float*,
-                           long long, float*, long long, int, int, int, int, unsigned long long,
-                           unsigned int, float, long long, long long, float*, float*, unsigned*,
-                           hipStream_t);
-hipError_t lumen_embedding(const void*, const long long*, void*, int, int, int, hipStream_t);
-hipError_t lumen_lora3_down(int, const void*, long long, const float*, long long, float*, long long,
-                            int, int, int, float, unsigned long long, unsigned int, float, long long,
-                            long long, void*, long long, int, int, unsigned*, float*, hipStream_t);
-hipError_t lumen_lora3_up(int, int, void*, long long, const float*, long long, const float*,
-                          long long, int, int, float, unsigned long long, unsigned int, float,
-                          long long, long long, int, const long long*, const long long*,
-                          const long long*, const int*, const float*, const float*, const int*,
-                          int, hipStream_t);
-hipError_t lumen_lora3_dy(int, const void*, long long, const float*, int, const float*, long long,
-                          float*, long long, float*, int, int, float, int, const long long*,
-                          const long long*, const long long*, const int*, float*, float*,
-                          unsigned*, unsigned*, hipStream_t);
-hipError_t lumen_transpose(int, const void*, void*, int, int, long long, long long, hipStream_t);
-hipError_t lumen_rope_cache(int, void*, long long, const int*, const float*, const float*, void*,
-                            void*, const long long*, int, int, int, int, int, int, hipStream_t);
-hipError_t lumen_skinny_swiglu_gemm(int, const void*, const void*, void*, int, int, int, long long,
-                                    long long, hipStream_t);
-hipError_t lumen_skinny_gemm(int, const void*, const void*, void*, int, int, int, long long,
-                             long long, hipStream_t);
-hipError_t lumen_decode_gemm(int, const void*, const void*, void*, float*, int*, int, int, int,
-                             long long, long long, int, int, int, int, int, hipStream_t);
-hipError_t lumen_w8_gemv(int, const void*, const void*, const float*, void*, int, int, int,
-                         long long, long long, hipStream_t);
-hipError_t lumen_w8_decode_gemm(int, const void*, const void*, const float*, void*, float*, int*,
-                                int, int, int, long long, long long, int, int, int, hipStream_t);
-hipError_t lumen_w8_dequant(int, const void*, const float*, void*, long long, long long,
-                            hipStream_t);
-hipError_t lumen_act_quant_fp8(int, const void*, void*, float*, int, int, long long, hipStream_t);
-hipError_t lumen_w8a8_gemv(int, const void*, const float*, const void*, const float*, void*, int,
-                           int, int, long long, long long, hipStream_t);
-hipError_t lumen_w8a8_decode_gemm(int, const void*, const float*, const void*, const float*, void*,
-                                  float*, int*, int, int, int, long long, long long, int, int, int,
-                                  int, hipStream_t);
-hipError_t lumen_w8a8_gemm(int, const void*, const float*, const void*, const float*, void*, int,
-                           int, int, long long, long long, hipStream_t);
-hipError_t lumen_w4a8_decode_gemm(int, const void*, const float*, const void*, const void*, void*,
-                                  float*, int*, int, int, int, long long, long long, int, int, int,
-                                  hipStream_t);
-hipError_t lumen_w4_dequant(int, const void*, const void*, void*, long long, long long,
-                            hipStream_t);
-hipError_t lumen_qbase_dequant(int, int, const void*, const void*, void*, long long, long long,
-                               long long, hipStream_t);
-hipError_t lumen_qbase_dequant_t(int, int, const void*, const void*, void*, long long, long long,
-                                 hipStream_t);
-hipError_t lumen_w4a16_gemv(int, const void*, const void*, const void*, void*, int, int, int,
-                            long long, long long, int, hipStream_t);
-hipError_t lumen_w4a16_decode_gemm(int, const void*, const void*, const void*, void*, float*, int*,
-                                   int, int, int, long long, long long, int, int, int,
-                                   hipStream_t);
-hipError_t lumen_mlp_gemm(int, int, const void*, long long, const void*, long long, void*, long long,
-                          void*, long long, const void*, long long, int, int, int, int, int, float*,
-                          int*, int, hipStream_t);
-int lumen_mlp_gemm_split(int, int, int, int, int);
-hipError_t lumen_hbm_read(const void*, long long, unsigned*, int, hipStream_t);
-void lumen_set_gemv_form(int);
-void lumen_set_rms_lds(int, int);
-hipError_t lumen_paged_attention_decode(int, void*, const void*, const void*, const void*,
-                                        const int*, const int*, int, int, int, int, int, int, int,
-                                        float, float*, float*, void*, int, unsigned*, int, int,
-                                        int, hipStream_t);
-hipError_t lumen_kv_dequant(int, const void*, const void*, void*, void*, const int*, int,
-                            const int*, int, int, int, int, int, hipStream_t);
-hipError_t lumen_kv_dequant_mx(int, const void*, const void*, void*, void*, const int*, int,
-                               const int*, int, int, int, int, int, hipStream_t);
-hipError_t lumen_reshape_and_cache(int, const void*, const void*, void*, void*, const long long*,
-                                   int, int, int, int, long long, long long, int, hipStream_t);
-hipError_t lumen_sample(int, const void*, const float*, const float*, const int*,
-                        unsigned long long, long long, long long*, float*, float*, int, int,
-                        hipStream_t);
-hipError_t lumen_sample_rows(int, const void*, const float*, const float*, const int*,
-                             const long long*, const long long*, const long long*, const float*,
-                             const int*, const int*, const float*, const int*, const float*,
-                             const float*, const float*, int*, int, int, long long*, float*,
-                             float*, int, int, hipStream_t);
-hipError_t lumen_logits_process(int, const void*, const int*, const int*, const float*, const int*,
-                                const float*, const float*, const float*, const int*, int, float*,
-                                int, int, hipStream_t);
-hipError_t lumen_sampler_state_init(int*, const int*, const int*, const int*, const int*, int, int,
-                                    int, hipStream_t);
-hipError_t lumen_flash_attn_paged(int, int, const void*, long long, const void*, const void*, void*,
-                                  long long, const int*, const int*, const int*, int, const int*,
-                                  int, int, int, int, int, float, hipStream_t);
-hipError_t lumen_flash_attn(int, int, int, int, const void*, const void*, const void*, long long,
-                            long long, long long, void*, long long, float*, const int*, const int*,
-                            int, int, int, int, float, const void*, long long, void*, void*, void*,
-                            long long, long long, long long, const float*, const int*, const float*,
-                            const float*, hipStream_t);
-hipError_t lumen_flash_attn_ds(int, int, int, const void*, const void*, const void*, long long,
-                               long long, long long, const float*, const int*, const int*, int, int,
-                               int, int, float, const void*, long long, void*, void*, void*,
-                               long long, long long, long long, const float*, const int*,
-                               const float*, const float*, void*, const int*, int, hipStream_t);
-long long lumen_car_signal_bytes();
-int lumen_car_max_blocks();
-int lumen_car_max_ranks();
-hipError_t lumen_car_alloc(long long, int, void**);
-hipError_t lumen_car_free(void*);
-hipError_t lumen_car_get_handle(void*, void*);
-int lumen_car_handle_bytes();
-hipError_t lumen_car_open_handle(const void*, void**);
-hipError_t lumen_car_close_handle(void*);
-hipError_t lumen_car_read_err(void*, unsigned int*);
-hipError_t lumen_car_read_diag(void*, unsigned int*);
-hipError_t lumen_car_allreduce(int, const long long*, const long long*, int, int, const void*,
-                               void*, long long, int, int, double, void*, hipStream_t);
-hipError_t lumen_car_allgather(int, const long long*, const long long*, int, int, const void*,
-                               void*, long long, long long, int, double, void*, hipStream_t);
-hipError_t lumen_car_host_flag_alloc(void**, void**);
-hipError_t lumen_car_host_flag_free(void*);
-void lumen_cpu_adamw(float*, const float*, float*, float*, long long, float, float, float, float,
-                     float, float, float, float);
-int lumen_cpu_has_avx512();
-}
+#include "cpu/cpu_adam.h"
+#include "kernels/api.h"
 
 namespace {
 
@@ -303,6 +155,39 @@ void need_splitk(const std::optional<at::Tensor>& ws, const std::optional<at::Te
     throw std::invalid_argument(std::string("lumen: ") + what + " split-K workspace too small");
 }
 
+// the launchers' (ws, cnt) arguments: null unless the launch is split
+float* ws_ptr(const std::optional<at::Tensor>& ws, int64_t s) {
+  return s > 1 ? ws->data_ptr<float>() : nullptr;
+}
+int* cnt_ptr(const std::optional<at::Tensor>& cnt, int64_t s) {
+  return s > 1 ? cnt->data_ptr<int>() : nullptr;
+}
+
+int i32(int64_t v) { return static_cast<int>(v); }
+
+// the compiled tiles of each decode-GEMM family, expanded from its list in kernels/api.h
+struct Tile { int bm, bn, waves; };
+#define LUMEN_TILE4(bm, bn, wm, wn) {bm, bn, (wm) * (wn)},
+#define LUMEN_TILE2(bm, bn) {bm, bn, 4},
+const std::vector<Tile> kDgTiles = {LUMEN_DG_VARIANTS(LUMEN_TILE4)};
+const std::vector<Tile> kDgXtTiles = {LUMEN_DG_XT_VARIANTS(LUMEN_TILE4)};
+const std::vector<Tile> kW8Tiles = {LUMEN_W8_VARIANTS(LUMEN_TILE2)};
+const std::vector<Tile> kW8A8Tiles = {LUMEN_W8A8_VARIANTS(LUMEN_TILE2)};
+const std::vector<Tile> kW4A8Tiles = {LUMEN_W4A8_VARIANTS(LUMEN_TILE2)};
+const std::vector<Tile> kW4A16Tiles = {LUMEN_W4A16_VARIANTS(LUMEN_TILE2)};
+#undef LUMEN_TILE4
+#undef LUMEN_TILE2
+
+// refuses a (bm, bn) that ``tiles`` does not hold, naming the pairs it does
+void need_variant(const std::vector<Tile>& tiles, int64_t bm, int64_t bn, const char* what) {
+  std::string pairs;
+  for (const Tile& t : tiles) {
+    if (t.bm == bm && t.bn == bn) return;
+    pairs += (pairs.empty() ? "(" : ", (") + std::to_string(t.bm) + ", " + std::to_string(t.bn) + ")";
+  }
+  throw std::invalid_argument(std::string("lumen: ") + what + " (bm, bn) must be one of " + pairs);
+}
+
 // decode-batch MFMA GEMM (kernels/decode_gemm.hip): y = x @ w^T with block tile (bm, bn) and
 // split-K s (s > 1: ws f32 slabs + cnt zeroed tile counters)
 void decode_gemm(const at::Tensor& x, const at::Tensor& w, at::Tensor& y,
@@ -321,13 +206,10 @@ void decode_gemm(const at::Tensor& x, const at::Tensor& w, at::Tensor& y,
       y.scalar_type() != w.scalar_type())
     throw std::invalid_argument("lumen: decode_gemm shape/layout mismatch");
   need_splitk(ws, cnt, x, (w.size(0) + bn - 1) / bn, s, bm, bn, "decode_gemm");
-  check(lumen_decode_gemm(dcode(w), x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                          s > 1 ? ws->data_ptr<float>() : nullptr,
-                          s > 1 ? cnt->data_ptr<int>() : nullptr, static_cast<int>(y.size(0)),
-                          static_cast<int>(w.size(0)), static_cast<int>(w.size(1)),
-                          xt ? w.size(1) : x.stride(0), y.stride(0), static_cast<int>(bm),
-                          static_cast<int>(bn), static_cast<int>(nw), static_cast<int>(s),
-                          static_cast<int>(flags), cur_stream()),
+  check(lumen_decode_gemm(dcode(w), x.data_ptr(), w.data_ptr(), y.data_ptr(), ws_ptr(ws, s),
+                          cnt_ptr(cnt, s), i32(y.size(0)), i32(w.size(0)), i32(w.size(1)),
+                          xt ? w.size(1) : x.stride(0), y.stride(0), i32(bm), i32(bn), i32(nw),
+                          i32(s), i32(flags), cur_stream()),
         "decode_gemm");
 }
 
@@ -370,11 +252,7 @@ void w8_decode_gemm(const at::Tensor& x, const at::Tensor& q, const at::Tensor& 
                     const std::optional<at::Tensor>& cnt, int64_t bm, int64_t bn, int64_t s) {
   need_w8(q, scale, "w8_decode_gemm");
   need_w8_xy(x, q, y, "w8_decode_gemm");
-  const bool variant = (bm == 64 && (bn == 64 || bn == 128)) ||
-                       (bm == 128 && (bn == 64 || bn == 128)) || (bm == 256 && bn == 64);
-  if (!variant)
-    throw std::invalid_argument("lumen: w8_decode_gemm (bm, bn) must be one of (64, 64), "
-                                "(64, 128), (128, 64), (128, 128), (256, 64)");
+  need_variant(kW8Tiles, bm, bn, "w8_decode_gemm");
   if (x.size(0) < 1 || x.size(0) > bm)
     throw std::invalid_argument("lumen: w8_decode_gemm needs 1 <= M <= bm");
   if (q.size(1) % 64 != 0 || q.size(0) % 4 != 0 || x.stride(0) % 8 != 0 ||
@@ -386,11 +264,9 @@ void w8_decode_gemm(const at::Tensor& x, const at::Tensor& q, const at::Tensor& 
     throw std::invalid_argument("lumen: w8_decode_gemm needs 1 <= s <= K / 64");
   need_splitk(ws, cnt, x, (q.size(0) + bn - 1) / bn, s, bm, bn, "w8_decode_gemm");
   check(lumen_w8_decode_gemm(dcode(x), x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(),
-                             y.data_ptr(), s > 1 ? ws->data_ptr<float>() : nullptr,
-                             s > 1 ? cnt->data_ptr<int>() : nullptr, static_cast<int>(x.size(0)),
-                             static_cast<int>(q.size(0)), static_cast<int>(q.size(1)),
-                             x.stride(0), y.stride(0), static_cast<int>(bm), static_cast<int>(bn),
-                             static_cast<int>(s), cur_stream()),
+                             y.data_ptr(), ws_ptr(ws, s), cnt_ptr(cnt, s), i32(x.size(0)),
+                             i32(q.size(0)), i32(q.size(1)), x.stride(0), y.stride(0), i32(bm),
+                             i32(bn), i32(s), cur_stream()),
         "w8_decode_gemm");
 }
 
@@ -463,13 +339,7 @@ void w8a8_decode_gemm(const at::Tensor& xq, const at::Tensor& sx, const at::Tens
                       int64_t form) {
   need_w8(q, scale, "w8a8_decode_gemm");
   need_w8a8(xq, sx, q, y, "w8a8_decode_gemm");
-  const bool variant = (bm == 64 && (bn == 64 || bn == 128)) ||
-                       (bm == 128 && (bn == 64 || bn == 128 || bn == 256)) ||
-                       (bm == 256 && (bn == 64 || bn == 128));
-  if (!variant)
-    throw std::invalid_argument("lumen: w8a8_decode_gemm (bm, bn) must be one of (64, 64), "
-                                "(64, 128), (128, 64), (128, 128), (128, 256), (256, 64), "
-                                "(256, 128)");
+  need_variant(kW8A8Tiles, bm, bn, "w8a8_decode_gemm");
   if (xq.size(0) > bm) throw std::invalid_argument("lumen: w8a8_decode_gemm needs 1 <= M <= bm");
   if (y.stride(0) % 4 != 0)
     throw std::invalid_argument("lumen: w8a8_decode_gemm needs a y row stride that is a multiple "
@@ -481,13 +351,10 @@ void w8a8_decode_gemm(const at::Tensor& xq, const at::Tensor& sx, const at::Tens
                                 "1 (non-scaled K = 32 MFMA)");
   need_splitk(ws, cnt, xq, (q.size(0) + bn - 1) / bn, s, bm, bn, "w8a8_decode_gemm");
   check(lumen_w8a8_decode_gemm(dcode(y), xq.data_ptr(), sx.data_ptr<float>(), q.data_ptr(),
-                               scale.data_ptr<float>(), y.data_ptr(),
-                               s > 1 ? ws->data_ptr<float>() : nullptr,
-                               s > 1 ? cnt->data_ptr<int>() : nullptr,
-                               static_cast<int>(xq.size(0)), static_cast<int>(q.size(0)),
-                               static_cast<int>(q.size(1)), xq.stride(0), y.stride(0),
-                               static_cast<int>(bm), static_cast<int>(bn), static_cast<int>(s),
-                               static_cast<int>(form), cur_stream()),
+                               scale.data_ptr<float>(), y.data_ptr(), ws_ptr(ws, s),
+                               cnt_ptr(cnt, s), i32(xq.size(0)), i32(q.size(0)), i32(q.size(1)),
+                               xq.stride(0), y.stride(0), i32(bm), i32(bn), i32(s), i32(form),
+                               cur_stream()),
         "w8a8_decode_gemm");
 }
 
@@ -538,23 +405,15 @@ void w4a8_decode_gemm(const at::Tensor& xq, const at::Tensor& sx, const at::Tens
     throw std::invalid_argument("lumen: w4a8_decode_gemm needs M >= 1, N % 4 == 0, K % 16 == 0, an "
                                 "xq row stride >= K that is a multiple of 16 and a y row stride "
                                 "that is a multiple of 4");
-  const bool variant = ((bm == 16 || bm == 64 || bm == 128) && (bn == 64 || bn == 128)) ||
-                       (bm == 256 && bn == 64);
-  if (!variant)
-    throw std::invalid_argument("lumen: w4a8_decode_gemm (bm, bn) must be one of (16, 64), "
-                                "(16, 128), (64, 64), (64, 128), (128, 64), (128, 128), (256, 64)");
+  need_variant(kW4A8Tiles, bm, bn, what);
   if (xq.size(0) > bm) throw std::invalid_argument("lumen: w4a8_decode_gemm needs 1 <= M <= bm");
   if (s < 1 || s > (K + 127) / 128)
     throw std::invalid_argument("lumen: w4a8_decode_gemm needs 1 <= s <= ceil(K / 128)");
   need_splitk(ws, cnt, xq, (N + bn - 1) / bn, s, bm, bn, "w4a8_decode_gemm");
   check(lumen_w4a8_decode_gemm(dcode(y), xq.data_ptr(), sx.data_ptr<float>(), q.data_ptr(),
-                               scale.data_ptr(), y.data_ptr(),
-                               s > 1 ? ws->data_ptr<float>() : nullptr,
-                               s > 1 ? cnt->data_ptr<int>() : nullptr,
-                               static_cast<int>(xq.size(0)), static_cast<int>(N),
-                               static_cast<int>(K), xq.stride(0), y.stride(0),
-                               static_cast<int>(bm), static_cast<int>(bn), static_cast<int>(s),
-                               cur_stream()),
+                               scale.data_ptr(), y.data_ptr(), ws_ptr(ws, s), cnt_ptr(cnt, s),
+                               i32(xq.size(0)), i32(N), i32(K), xq.stride(0), y.stride(0),
+                               i32(bm), i32(bn), i32(s), cur_stream()),
         what);
 }
 
@@ -668,11 +527,7 @@ void w4a16_decode_gemm(const at::Tensor& x, const at::Tensor& q, const at::Tenso
                        const std::optional<at::Tensor>& cnt, int64_t bm, int64_t bn, int64_t s) {
   need_w4a16(x, q, scale, y, "w4a16_decode_gemm");
   const int64_t K = x.size(1), N = q.size(0);
-  const bool variant = ((bm == 64 || bm == 128) && (bn == 64 || bn == 128)) ||
-                       (bm == 256 && bn == 64);
-  if (!variant)
-    throw std::invalid_argument("lumen: w4a16_decode_gemm (bm, bn) must be one of (64, 64), "
-                                "(64, 128), (128, 64), (128, 128), (256, 64)");
+  need_variant(kW4A16Tiles, bm, bn, "w4a16_decode_gemm");
   if (x.size(0) < 1 || x.size(0) > bm)
     throw std::invalid_argument("lumen: w4a16_decode_gemm needs 1 <= M <= bm");
   if (K % 32 != 0 || N % 4 != 0 || x.stride(0) % 8 != 0 || x.stride(0) < K ||
@@ -684,11 +539,8 @@ void w4a16_decode_gemm(const at::Tensor& x, const at::Tensor& q, const at::Tenso
     throw std::invalid_argument("lumen: w4a16_decode_gemm needs 1 <= s <= ceil(K / 64)");
   need_splitk(ws, cnt, x, (N + bn - 1) / bn, s, bm, bn, "w4a16_decode_gemm");
   check(lumen_w4a16_decode_gemm(dcode(x), x.data_ptr(), q.data_ptr(), scale.data_ptr(),
-                                y.data_ptr(), s > 1 ? ws->data_ptr<float>() : nullptr,
-                                s > 1 ? cnt->data_ptr<int>() : nullptr,
-                                static_cast<int>(x.size(0)), static_cast<int>(N),
-                                static_cast<int>(K), x.stride(0), y.stride(0),
-                                static_cast<int>(bm), static_cast<int>(bn), static_cast<int>(s),
+                                y.data_ptr(), ws_ptr(ws, s), cnt_ptr(cnt, s), i32(x.size(0)),
+                                i32(N), i32(K), x.stride(0), y.stride(0), i32(bm), i32(bn), i32(s),
                                 cur_stream()),
         "w4a16_decode_gemm");
 }
@@ -1595,8 +1447,27 @@ void car_allreduce(const std::vector<int64_t>& data, const std::vector<int64_t>&
         "car_allreduce");
 }
 
+// {family: [(bm, bn, waves)] for the 16-bit decode GEMM, [(bm, bn)] for the quantized ones}
+py::dict variants() {
+  auto tuples = [](const std::vector<Tile>& tiles, bool waves) {
+    py::list l;
+    for (const Tile& t : tiles)
+      l.append(waves ? py::make_tuple(t.bm, t.bn, t.waves) : py::make_tuple(t.bm, t.bn));
+    return l;
+  };
+  py::dict d;
+  d["decode_gemm"] = tuples(kDgTiles, true);
+  d["decode_gemm_xt"] = tuples(kDgXtTiles, true);
+  d["w8_decode_gemm"] = tuples(kW8Tiles, false);
+  d["w8a8_decode_gemm"] = tuples(kW8A8Tiles, false);
+  d["w4a8_decode_gemm"] = tuples(kW4A8Tiles, false);
+  d["w4a16_decode_gemm"] = tuples(kW4A16Tiles, false);
+  return d;
+}
+
 PYBIND11_MODULE(_C, m) {
   m.doc() = "lumen native ops for MI355X (gfx950)";
+  m.def("variants", &variants);
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("lora3_down", &lora3_down, py::arg("x"), py::arg("ldx"), py::arg("A"), py::arg("Z"),
         py::arg("ldz"), py::arg("T"), py::arg("K"), py::arg("R"), py::arg("alpha"), py::arg("seed"),

@@ -4,7 +4,8 @@
   targets, no CUDA, no hipify) -- these translation units include only HIP headers, so they
   rebuild in seconds;
 * ``cpu/cpu_adam.cpp`` (host AdamW for ZeRO-Offload) by the host compiler with OpenMP;
-* ``binding.cpp`` (pybind11 + torch headers, the slow one) only when it changed;
+* ``binding.cpp`` (pybind11 + torch headers, the slow one) only when it or one of its two
+  headers (``kernels/api.h``, ``cpu/cpu_adam.h``) changed;
 * linked into one shared object next to ``lumen/__init__.py`` so it travels with the repo
   snapshot to the GPU box (no JIT cache under ~/.cache).
 
@@ -57,7 +58,8 @@ def sources() -> list:
     """Every source the extension is built from (kernels, headers, host code, binding)."""
     return sorted(glob.glob(os.path.join(HERE, "kernels", "*.hip"))
                   + glob.glob(os.path.join(HERE, "kernels", "*.h"))
-                  + [os.path.join(HERE, "cpu", "cpu_adam.cpp"), os.path.join(HERE, "binding.cpp")])
+                  + [os.path.join(HERE, "cpu", f) for f in ("cpu_adam.cpp", "cpu_adam.h")]
+                  + [os.path.join(HERE, "binding.cpp")])
 
 
 def source_digest() -> dict:
@@ -152,16 +154,17 @@ def _build_locked(jobs, force, asm, verbose, build_dir, out) -> str:
                 cmd.insert(1, "-save-temps")
             jobs_list.append(cmd)
     cpu_src = os.path.join(HERE, "cpu", "cpu_adam.cpp")
+    cpu_hdr = os.path.join(HERE, "cpu", "cpu_adam.h")
     cpu_obj = os.path.join(build_dir, "cpu_adam.o")
     objs.append(cpu_obj)
-    if force or _newer([cpu_src], cpu_obj):
+    if force or _newer([cpu_src, cpu_hdr], cpu_obj):
         jobs_list.append(["g++", "-O3", "-fPIC", "-std=c++17", "-fopenmp", "-c", cpu_src, "-o",
                           cpu_obj])
     bind_src = os.path.join(HERE, "binding.cpp")
     bind_obj = os.path.join(build_dir, "binding.o")
     objs.append(bind_obj)
     cflags, ldflags = _torch_flags()
-    if force or _newer([bind_src], bind_obj):
+    if force or _newer([bind_src, cpu_hdr, os.path.join(HERE, "kernels", "api.h")], bind_obj):
         # host-only translation unit: plain g++ against the HIP host API headers
         jobs_list.append(["g++", "-O2", "-fPIC", "-std=c++17", f"-I{ROCM}/include", *cflags, "-c",
                           bind_src, "-o", bind_obj])

@@ -12,6 +12,8 @@
 #include <cstdint>
 #include <immintrin.h>
 
+#include "cpu_adam.h"
+
 namespace {
 
 inline void adam_scalar(float* p, const float* g, float* m, float* v, long long i0, long long i1,

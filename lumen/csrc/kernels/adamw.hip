@@ -13,6 +13,7 @@
 //    min(1, max_norm/||g||) and the skip-on-overflow decision into the update itself, so a bf16
 //    step needs no device->host synchronisation at all; optionally it writes a 16-bit copy of the
 //    updated parameters in the same pass (the "fp32 master -> bf16 model" copy-out).
+#include "api.h"
 #include "common.h"
 #include "det.h"
 

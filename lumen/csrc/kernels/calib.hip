@@ -3,6 +3,7 @@
 // so a slow record can be told apart from a slow box (same process, same lease).  The loop is
 // scripts/probes/hbm_read_probe.cpp's: 16-byte non-temporal loads, 8 in flight per lane,
 // grid-stride, folded into one word so the loads stay.
+#include "api.h"
 #include "common.h"
 
 namespace lumen {

@@ -5,7 +5,7 @@
 //  * 16-bit activations (bf16 / fp16) are moved as 16-byte vectors (8 elements per lane),
 //    converted to f32 in registers and accumulated in f32.
 //  * launchers are `extern "C"` functions that take raw pointers + a hipStream_t and never
-//    allocate or synchronise (safe under hipGraph capture).
+//    allocate or synchronise (safe under hipGraph capture); each is declared once, in api.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>

@@ -13,6 +13,7 @@
 // fp16 with dynamic loss scaling: `gscale` (device f32, optional) multiplies the written gradient
 // by the CURRENT loss scale, as the reference's upcast-logits graph does ((p - y) * S / n reaches
 // the fp16 LM-head GEMM already scaled); without it p / n underflows fp16 for most of the vocab.
+#include "api.h"
 #include "common.h"
 
 namespace lumen {

@@ -35,6 +35,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "api.h"
 #include "common.h"
 
 using namespace lumen;

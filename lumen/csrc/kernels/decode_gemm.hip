@@ -22,6 +22,7 @@
 //    output columns of one row: 8-byte stores;
 //  * split-K (S > 1) is reduced in the launch and the blocks are mapped to (tile, slice) under
 //    the XCD-aware remap: see dgemm.h.
+#include "api.h"
 #include "common.h"
 #include "dgemm.h"
 
@@ -194,18 +195,8 @@ dgemm_kernel(const T* __restrict__ x, const T* __restrict__ W, T* __restrict__ y
   }
 }
 
-// compiled (BM, BN, waves) variants.  4 waves, WM x WN: BM 256 -> 4 x 1, 128 -> 2 x 2,
-// 64 -> 1 x 4; 8 waves: BM 256 -> 4 x 2, 128 -> 2 x 4
-#define LUMEN_DG_VARIANTS(X)                                                                   \
-  X(256, 64, 4, 1) X(256, 96, 4, 1) X(256, 128, 4, 1) X(256, 160, 4, 1)                         \
-  X(192, 64, 4, 1) X(192, 96, 4, 1) X(192, 128, 4, 1)                                           \
-  X(128, 64, 2, 2) X(128, 96, 2, 2) X(128, 128, 2, 2) X(128, 192, 2, 2) X(128, 256, 2, 2)       \
-  X(64, 64, 1, 4) X(64, 128, 1, 4) X(64, 192, 1, 4) X(64, 256, 1, 4)                            \
-  X(256, 64, 4, 2) X(256, 128, 4, 2) X(128, 128, 2, 4) X(128, 256, 2, 4)
-
-// k-tiled x variants (flags bit 1): the BM = 256 tiles
-#define LUMEN_DG_XT_VARIANTS(X) X(256, 64, 4, 1) X(256, 128, 4, 1) X(256, 64, 4, 2) X(256, 128, 4, 2)
-
+// one launch per compiled (BM, BN, WM x WN) variant: the lists LUMEN_DG_VARIANTS and
+// LUMEN_DG_XT_VARIANTS (k-tiled x, flags bit 1) in api.h
 template <typename T>
 hipError_t launch(const void* x, const void* W, void* y, float* ws, int* cnt, int M, int N, int K,
                   long long ldx, long long ldy, int BM, int BN, int NW, int S, int flags,

@@ -6,6 +6,7 @@
 // copies ROWS rows (one wave per row, 64 lanes x 16 B = 1 KiB per instruction), with every
 // load of the block issued before the first store.  Out-of-range ids (padding / ignored
 // positions) produce zero rows instead of faulting.
+#include "api.h"
 #include "common.h"
 
 namespace lumen {

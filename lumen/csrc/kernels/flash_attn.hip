@@ -20,6 +20,7 @@
 //        in registers, loops over query tiles and the GQA group's heads), and dQ per 64-query
 //        tile (loops over key tiles); the softmax row statistics come from the forward's LSE
 //        and delta = rowsum(dO * O) (preprocess kernel).
+#include "api.h"
 #include "common.h"
 #include <cstdlib>
 

@@ -24,6 +24,7 @@
 // Tile: BM = 64 rows (4 waves x 16), BN = 16 or 64 columns, BK = 32; blockIdx.z enumerates
 // (segment, K-split).  LDS rows are padded to 34 floats so the MFMA operand reads
 // (lanes = 16 rows x 2 k) hit 32 distinct banks.
+#include "api.h"
 #include "common.h"
 
 namespace lumen {

@@ -19,6 +19,7 @@
 // way in, so the backward regenerates the forward's mask from the same hash) and the small one
 // as a padded bf16 LDS tile; each block owns a 128-wide slice of the non-reduced axis and a
 // split of the reduced one, and lands its partial sums with 64-byte-coalesced f32 atomics.
+#include "api.h"
 #include "tile128.h"
 
 namespace lumen {

@@ -20,6 +20,7 @@
 //
 // Dropout is the same counter hash as lora_v2 (common.h dropout_keep8), so masks regenerate
 // bit-identically across kernels and against lumen.ops.lora.dropout_mask_ref.
+#include "api.h"
 #include "tile128.h"
 #include "det.h"
 

@@ -25,6 +25,7 @@
 // are four consecutive output columns of one row: 8-byte stores.  Block ids are remapped
 // XCD-aware (the blocks of one XCD get consecutive tiles) and tiles are visited in groups of
 // GROUP_M row tiles, so the blocks that run together on an XCD share x and W panels in its L2.
+#include "api.h"
 #include "common.h"
 
 namespace lumen {

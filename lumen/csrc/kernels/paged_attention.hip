@@ -14,6 +14,7 @@
 // rows per step; q lives in LDS (f32, pre-scaled); scores for the partition stay in LDS; softmax
 // is one wave per head; P.V accumulates per lane then reduces through LDS.  Contexts longer than
 // one partition write unnormalised (m, l, o) partials that `pa_reduce_kernel` merges.
+#include "api.h"
 #include "common.h"
 #include "mxfp4.h"
 

@@ -14,6 +14,7 @@
 // to the output type (w8_gemm.hip's w8_dequant arithmetic; v_cvt_scalef32_pk_*_fp8 is exact only
 // for the unscaled conversion, which is not what dequant() computes), MXFP4 is mxfp4.h's
 // v_cvt_scalef32_pk_*_fp4.  K % 16 == 0 and N % 8 == 0; every load and store is bounded by N and K.
+#include "api.h"
 #include "common.h"
 #include "mxfp4.h"
 

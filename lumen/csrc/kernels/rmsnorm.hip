@@ -15,6 +15,7 @@
 //       rstd[row] saved (f32) for backward
 // bwd:  g = dy * w;  ds = rstd * (g - s*rstd * mean(g * s*rstd)) (+ ds_residual)
 //       dw (optional) += sum_rows(dy * s * rstd)  (f32, per-block partials then atomics)
+#include "api.h"
 #include "common.h"
 
 #include <cstdlib>

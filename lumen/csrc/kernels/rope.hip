@@ -13,6 +13,7 @@
 //
 // Thread mapping: one thread = 8 rotation pairs (16 elements, two 16-byte vectors) of one
 // (token, head); v heads are plain 16-element copies.
+#include "api.h"
 #include "common.h"
 
 namespace lumen {

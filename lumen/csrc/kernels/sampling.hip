@@ -21,6 +21,7 @@
 // temperature == 0 -> greedy argmax.  Also returns the chosen token's log-prob under the
 // temperature-scaled (untruncated) distribution, and optionally the kept threshold (as a
 // value of z) for tests.
+#include "api.h"
 #include "sampling_common.h"
 
 namespace lumen {

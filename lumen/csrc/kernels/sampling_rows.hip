@@ -17,6 +17,7 @@
 // Same structure as sampling.hip: one 512-thread workgroup per row, the row in LDS for
 // V <= 32768.  Larger vocabularies go through lumen_logits_process into an f32 scratch and the
 // no-LDS form over it (`pre` = the logits are already processed).
+#include "api.h"
 #include "sampling_common.h"
 
 namespace lumen {

@@ -14,6 +14,7 @@
 //    the MFMAs (U * 1 KiB per wave, 2U in flight), which is what keeps ~10 B/cycle/CU of HBM
 //    traffic going at one workgroup per CU;
 //  * the four K partials meet in LDS; wave 0 writes the M x 16 output tile.
+#include "api.h"
 #include "common.h"
 #include "dgemm.h"
 #include "gemv.h"

@@ -4,6 +4,7 @@
 // silu + mul, two launches and an extra [T, F] round trip).  Here gate and up come from ONE fused
 // GEMM whose output row is [gate(F) | up(F)]; the kernel reads both halves with 16-byte vectors
 // and writes act, and the backward writes the fused [dgate | dup] row that feeds that GEMM's dX.
+#include "api.h"
 #include "common.h"
 
 namespace lumen {

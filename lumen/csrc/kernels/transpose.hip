@@ -6,6 +6,7 @@
 // strided copy reaches ~0.5 TB/s on these shapes.  Tile = 64 x 64 elements: 16-byte global loads
 // along the input rows, an LDS tile padded by one 16-bit element per row so that the transposed
 // reads of 8 rows x 1 column hit distinct banks, and 16-byte global stores along output rows.
+#include "api.h"
 #include "common.h"
 
 namespace lumen {

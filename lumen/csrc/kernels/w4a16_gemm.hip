@@ -20,6 +20,7 @@
 // them; word s of the two feeds MFMA s.  Element j of lane group g in MFMA s is therefore
 // k = k0 + 16 g + 8 s + j -- the permutation of kernels/w8_gemm.hip -- and x's B operand is read
 // from LDS at the same k (16-byte chunk 2 g + s of the stage).
+#include "api.h"
 #include "common.h"
 #include "dgemm.h"
 #include "gemv.h"
@@ -322,9 +323,7 @@ w4a16_dgemm_kernel(const T* __restrict__ x, const unsigned char* __restrict__ W,
   }
 }
 
-// compiled (BM, BN) variants, 4 waves each (lumen/ops/gemm.py W4A16_BNS lists the same)
-#define LUMEN_W4A16_VARIANTS(X) X(64, 64) X(64, 128) X(128, 64) X(128, 128) X(256, 64)
-
+// one launch per compiled (BM, BN) variant, 4 waves each: the list LUMEN_W4A16_VARIANTS in api.h
 template <typename T>
 hipError_t launch_dgemm(const void* x, const void* W, const void* scale, void* y, float* ws,
                         int* cnt, int M, int N, int K, long long ldx, long long ldy, int BM,

@@ -25,6 +25,7 @@
 // 16-byte x chunks past K are zero-filled in registers; W rows are stored padded to whole blocks
 // with zero nibbles (+0.0), whole 16-byte W chunks past that are zero-filled in registers with
 // scale 2^0.
+#include "api.h"
 #include "common.h"
 #include "dgemm.h"
 #include "mxfp4.h"
@@ -267,10 +268,7 @@ w4a8_dgemm_kernel(const unsigned char* __restrict__ xq, const float* __restrict_
   }
 }
 
-// compiled (BM, BN) variants, 4 waves each (lumen/ops/gemm.py W4A8_BNS lists the same)
-#define LUMEN_W4A8_VARIANTS(X) \
-  X(16, 64) X(16, 128) X(64, 64) X(64, 128) X(128, 64) X(128, 128) X(256, 64)
-
+// one launch per compiled (BM, BN) variant, 4 waves each: the list LUMEN_W4A8_VARIANTS in api.h
 template <typename T>
 hipError_t launch_dgemm(const void* xq, const float* sx, const void* W, const void* scale,
                         void* y, float* ws, int* cnt, int M, int N, int K, long long ldx,

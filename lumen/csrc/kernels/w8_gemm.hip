@@ -14,6 +14,7 @@
 //  * w8_dgemm_kernel    5 <= M <= 256: kernels/decode_gemm.hip's tile / split-K structure with
 //                       W streamed straight into the MFMA A operand;
 //  * w8_dequant_kernel  [N, K] fp8 + scales -> 16-bit [N, K].
+#include "api.h"
 #include "common.h"
 #include "dgemm.h"
 #include "gemv.h"
@@ -252,9 +253,7 @@ w8_dgemm_kernel(const T* __restrict__ x, const unsigned char* __restrict__ W,
   }
 }
 
-// compiled (BM, BN) variants, 4 waves each (lumen/ops/gemm.py W8_BNS lists the same)
-#define LUMEN_W8_VARIANTS(X) X(64, 64) X(64, 128) X(128, 64) X(128, 128) X(256, 64)
-
+// one launch per compiled (BM, BN) variant, 4 waves each: the list LUMEN_W8_VARIANTS in api.h
 template <typename T>
 hipError_t launch_dgemm(const void* x, const void* W, const float* scale, void* y, float* ws,
                         int* cnt, int M, int N, int K, long long ldx, long long ldy, int BM,

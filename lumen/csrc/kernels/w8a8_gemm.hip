@@ -23,6 +23,7 @@
 // assigns to A and B alike, so the sum over k does not depend on it (tests/test_w8a8_gpu.py proves
 // it with exact integer data).  K % 16 == 0: 16-byte chunks past K are zero-filled in registers /
 // LDS (a zero byte is 0.0 in e4m3).
+#include "api.h"
 #include "common.h"
 #include "dgemm.h"
 #include "gemv.h"
@@ -383,10 +384,7 @@ w8a8_dgemm_kernel(const unsigned char* __restrict__ xq, const float* __restrict_
   }
 }
 
-// compiled (BM, BN) variants, 4 waves each (lumen/ops/gemm.py W8A8_BNS lists the same)
-#define LUMEN_W8A8_VARIANTS(X) \
-  X(64, 64) X(64, 128) X(128, 64) X(128, 128) X(128, 256) X(256, 64) X(256, 128)
-
+// one launch per compiled (BM, BN) variant, 4 waves each: the list LUMEN_W8A8_VARIANTS in api.h
 template <typename T, bool SC>
 hipError_t launch_dgemm(const void* xq, const float* sx, const void* W, const float* scale,
                         void* y, float* ws, int* cnt, int M, int N, int K, long long ldx,

@@ -7,9 +7,7 @@
 #include <cstdlib>
 #include <vector>
 
-extern "C" void lumen_cpu_adamw(float* p, const float* g, float* m, float* v, long long n,
-                                float lr, float b1, float b2, float eps, float wd, float bc1,
-                                float bc2, float grad_scale);
+#include "../../lumen/csrc/cpu/cpu_adam.h"
 
 int main() {
   const long long sizes[] = {1, 15, 16, 17, 65535, 65536, 65537, 200003};

@@ -926,10 +926,38 @@ def test_decode_gemm_variants(bm):
             if bm == 256:
                 xt = x_ktiled(x)
                 for fl in (2, 3):
-                    for bn, nw in ((64, 4), (128, 4), (64, 8), (128, 8)):
+                    for xbm, bn, nw in native().variants()["decode_gemm_xt"]:
+                        assert xbm == bm
                         y = decode_gemm(xt, w, bm, bn, s, nw, flags=fl, m=M)
                         assert y.shape == (M, w.shape[0])
                         assert rel(y, ref) < 1e-2, (fl, bn, nw, s, M, rel(y, ref))
+
+
+def test_variant_tables_match_native():
+    """The tile tables of lumen/ops/gemm.py (what the tests, the benches and the plans iterate)
+    hold exactly the variants the extension compiled (kernels/api.h, read back through
+    ``_C.variants()``): a tile in one list only would be never tested or refused at run time.
+    No kernel is launched."""
+    import lumen.ops.gemm as gm
+    from lumen.ops._native import native
+
+    v = {k: [tuple(t) for t in ts] for k, ts in native().variants().items()}
+    pairs = lambda table: {(bm, bn) for bm, bns in table.items() for bn in bns}
+    want = {
+        "decode_gemm": ({(bm, bn, 4) for bm, bn in pairs(gm.DG_BNS)}
+                        | {(bm, bn, 8) for bm, bn in pairs(gm.DG_BNS8)}),
+        # gemm.py has no table for the k-tiled x layout: test_decode_gemm_variants runs this list
+        "decode_gemm_xt": {(256, 64, 4), (256, 128, 4), (256, 64, 8), (256, 128, 8)},
+        "w8_decode_gemm": pairs(gm.W8_BNS),
+        "w8a8_decode_gemm": pairs(gm.W8A8_BNS),
+        "w4a8_decode_gemm": pairs(gm.W4A8_BNS),
+        "w4a16_decode_gemm": pairs(gm.W4A16_BNS),
+    }
+    assert set(v) == set(want)
+    for family, tiles in want.items():
+        assert len(v[family]) == len(set(v[family])), family   # no variant listed twice
+        assert set(v[family]) == tiles, (family, set(v[family]) ^ tiles)
+    assert set(v["decode_gemm_xt"]) <= set(v["decode_gemm"])
 
 
 def test_splitk_families_share_workspace():

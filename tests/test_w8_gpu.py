@@ -104,6 +104,10 @@ def test_w8_decode_gemm_variants(bm):
         native().w8_decode_gemm(torch.zeros(bm + 1, K, device=DEV, dtype=torch.float16), qw.q,
                                 qw.scale, torch.empty(bm + 1, qw.shape[0], device=DEV,
                                                       dtype=torch.float16), None, None, bm, bn, 1)
+    # (64, 256) is not a compiled variant: refused by name before any launch
+    with pytest.raises(ValueError, match=r"\(bm, bn\) must be one of \(64, 64\)"):
+        native().w8_decode_gemm(x[:5], qw.q, qw.scale, torch.empty_like(y[:5]), None, None, 64,
+                                256, 1)
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])

@@ -204,6 +204,10 @@ def test_w8a8_decode_gemm_variants(bm, form):
         native().w8a8_decode_gemm(rq, rs, rw.q, rw.scale, torch.empty_like(ref), ws, cnt, bm, bn,
                                   K // 64 + 1, form)
     assert int(cnt.abs().sum()) == 0
+    # (64, 256) is not a compiled variant: refused by name before any launch
+    with pytest.raises(ValueError, match=r"\(bm, bn\) must be one of \(64, 64\)"):
+        native().w8a8_decode_gemm(rq[:5], rs[:5], rw.q, rw.scale, torch.empty_like(ref[:5]), None,
+                                  None, 64, 256, 1, form)
 
 
 # ---- the large-M kernel -------------------------------------------------------------------------
