@@ -5,6 +5,10 @@ to the host-side penalty path it replaces.  256 x 32000 bf16, T = 0.8, top-k 50,
   rows_off          sample_rows, nothing on (uniform seed / offset, rngrow = row)
   rows_on           sample_rows with penalties from the count table, 16 bias entries per row and
                     min_p 0.05
+  rows_guided       sample_rows with every row guided: one 64-state token table (int16
+                    [64, V], ~5 % of the tokens allowed in every state), the rows spread over
+                    the states; the extra traffic is one table row per logits row (16.4 MB a
+                    call at 256 x 32000)
   host_penalties    engine.apply_penalties on 256 sequences of 576 ids (512 prompt + 64
                     generated), then ``sample``: host wall time, ended by a synchronise
 
@@ -67,6 +71,13 @@ def main():
     rp = torch.full((R,), 1.1, device=dev)
     fp = torch.full((R,), 0.5, device=dev)
     pp = torch.full((R,), 0.2, device=dev)
+    # guided rows: a 64-state table, ~5 % of the tokens allowed, successors anywhere
+    GS = 64
+    g_next = torch.where(torch.rand(GS, V, generator=g) < 0.05,
+                         torch.randint(0, GS, (GS, V), generator=g), torch.tensor(-1))
+    g_next = g_next.to(torch.int16).to(dev)
+    g_table = torch.full((R,), g_next.data_ptr(), device=dev, dtype=torch.int64)
+    g_state = (torch.arange(R) % GS).to(torch.int32).to(dev)
     seqs = []
     for i in range(R):
         s = Sequence(prompt[i].tolist(), SamplingParams(frequency_penalty=0.5, presence_penalty=0.2,
@@ -86,10 +97,14 @@ def main():
                       bias_ptr=bias_ptr, bias_idx=bias_idx, bias_val=bias_val, slot=slots, rp=rp,
                       fp=fp, pp=pp, counts=counts, out_tokens=out, out_logprob=lp)
 
+    def k_guided():
+        C.sample_rows(logits, temp, top_p, top_k, seed, offset, rngrow, out_tokens=out,
+                      out_logprob=lp, g_table=g_table, g_slot=slots, g_state=g_state)
+
     def k_host():
         C.sample(apply_penalties(logits, seqs), temp, top_p, top_k, 7, 3, out, lp)
 
-    kernels = {"sample": k_sample, "rows_off": k_off, "rows_on": k_on}
+    kernels = {"sample": k_sample, "rows_off": k_off, "rows_on": k_on, "rows_guided": k_guided}
     for f in list(kernels.values()) + [k_host]:
         for _ in range(3):
             f()
@@ -119,7 +134,9 @@ def main():
                                "max": round(max(v), 2)} for k, v in times.items()},
            "host_penalties_us_per_call": {"median": round(statistics.median(host), 1),
                                           "min": round(min(host), 1), "max": round(max(host), 1)},
-           "state_table_mb": round(counts.numel() * 4 / 1e6, 1)}
+           "state_table_mb": round(counts.numel() * 4 / 1e6, 1),
+           "guided_table_states": GS, "guided_allowed_fraction": 0.05,
+           "guided_table_bytes_read_per_call": R * V * 2}
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

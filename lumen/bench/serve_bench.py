@@ -94,6 +94,11 @@ def bench_engine(a, eng=None) -> dict:
         params["frequency_penalty"] = a.frequency_penalty
     if getattr(a, "min_p", 0.0):
         params["min_p"] = a.min_p
+    # --guided-regex: every request constrained by the pattern (its token table is compiled at
+    # the first request and cached; the automaton state lives on the device)
+    guided = getattr(a, "guided_regex", None) if getattr(a, "guided_on", True) else None
+    if guided:
+        params["guided"] = ("regex", guided)
     per_seed = getattr(a, "seed_per_request", False)
     new_params = lambda i: SamplingParams(**params, **({"seed": 1000 + i} if per_seed else {}))  # noqa: E731
     # --shared-prefix N: every prompt starts with the same N tokens (a shared system prompt)
@@ -147,6 +152,7 @@ def bench_engine(a, eng=None) -> dict:
             "frequency_penalty": getattr(a, "frequency_penalty", 0.0),
             "min_p": getattr(a, "min_p", 0.0), "seed_per_request": per_seed,
             "sampler_state": getattr(eng, "dev_state", None),
+            "guided_regex": guided, "guided": eng.guided_stats() if guided else None,
             "quantization": getattr(a, "quantization", None),
             "hbm": getattr(eng, "_bench_hbm", None),
             "setup_s": round(getattr(eng, "_bench_setup_s", 0.0), 1),
@@ -323,6 +329,9 @@ def main():
                     help="http mode: OpenAI API processes sharing the port (SO_REUSEPORT)")
     ap.add_argument("--client-procs", type=int, default=1,
                     help="http mode: load-client processes (Locust-style workers)")
+    ap.add_argument("--guided-regex", default=None,
+                    help="engine mode: run the workload unguided and with every request guided "
+                         "by this regex, alternating on one engine (two rounds), and report both")
     ap.add_argument("--trace-steps", action="store_true",
                     help="engine mode: time every step synchronously, grouped by composition")
     a = ap.parse_args()
@@ -346,7 +355,21 @@ def main():
         print(json.dumps(res), flush=True)
         shutdown()
         return
-    if a.mode == "both":
+    if a.guided_regex and a.mode == "engine":
+        eng = make_engine(a)
+        keys = ("output_tok_s", "itl_p50_ms", "itl_p99_ms", "itl_mean_ms", "overlapped_steps",
+                "steps", "wall_s", "output_tokens")
+        runs = {"unguided": [], "guided": []}
+        for _ in range(2):              # alternate: drift hits both alike
+            for name in ("unguided", "guided"):
+                a.guided_on = name == "guided"
+                r = bench_engine(a, eng)
+                runs[name].append({k: r[k] for k in keys})
+        from lumen.serve.guided import compile_guided
+
+        res = dict(r, **{k: None for k in keys}, runs=runs, guided_regex=a.guided_regex,
+                   guided_states=compile_guided("regex", a.guided_regex).num_states)
+    elif a.mode == "both":
         eng = make_engine(a)
         res = bench_http(a, eng)
         res["engine"] = bench_engine(a, eng)

@@ -74,6 +74,12 @@ def build_parser():
     ap.add_argument("--ngram-prompt-lookup-max", type=int, default=4)
     ap.add_argument("--ngram-prompt-lookup-min", type=int, default=1)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--guided-max-states", type=int, default=4096,
+                    help="guided decoding: most automaton states a grammar may have (its token "
+                         "table is states x vocabulary x 2 bytes); larger ones answer 400")
+    ap.add_argument("--guided-cache-mb", type=int, default=1024,
+                    help="guided decoding: device memory for compiled token tables (LRU; a "
+                         "table in use is never evicted)")
     ap.add_argument("--api-server-count", type=int, default=1,
                     help="OpenAI API processes sharing --port (SO_REUSEPORT), each streaming its "
                          "own requests' tokens from the one engine core")
@@ -100,7 +106,8 @@ def main(argv=None):
         lora_names = [m.split("=", 1)[0] for m in (a.lora_modules or [])]
         req_q, out_qs, apis = start_api_servers(a.api_server_count, a.model, a.max_model_len,
                                                 a.host, a.port, a.served_model_name,
-                                                mcfg.vocab_size, lora_names)
+                                                mcfg.vocab_size, lora_names,
+                                                guided_max_states=a.guided_max_states)
 
     from lumen.parallel.dist import init
     from lumen.serve.engine import AsyncEngine, EngineConfig, LLMEngine
@@ -124,7 +131,8 @@ def main(argv=None):
                        num_speculative_tokens=spec_k,
                        ngram_max=a.ngram_prompt_lookup_max, ngram_min=a.ngram_prompt_lookup_min,
                        lora_modules=dict(m.split("=", 1) for m in a.lora_modules)
-                       if a.lora_modules else None, max_loras=a.max_loras)
+                       if a.lora_modules else None, max_loras=a.max_loras,
+                       guided_max_states=a.guided_max_states, guided_cache_mb=a.guided_cache_mb)
     eng = LLMEngine(cfg)
     if env.rank != 0:
         from lumen.serve.tp import worker_loop

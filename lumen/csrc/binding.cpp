@@ -1166,20 +1166,39 @@ void need_row_state(int rows, int V, const OptT& bias_ptr, const OptT& bias_idx,
     need_vec(pp, at::kFloat, rows, "pp");
   }
 }
+
+// guided rows: g_table int64 [rows] (device address of the row's int16 next[S][V], 0 = unguided),
+// g_slot int32 [rows], g_state int32 [G] -- all three or none
+void need_guided(int rows, const OptT& g_table, const OptT& g_slot, const OptT& g_state) {
+  if (!g_table && !g_slot && !g_state) return;
+  if (!g_table || !g_slot || !g_state || g_state->numel() < 1)
+    throw std::invalid_argument("lumen: sampling g_table, g_slot and g_state go together");
+  need_vec(g_table, at::kLong, rows, "g_table");
+  need_vec(g_slot, at::kInt, rows, "g_slot");
+  need_vec(g_state, at::kInt, 1, "g_state");
+}
+
+const long long* llptr(const OptT& t) {
+  return t ? reinterpret_cast<const long long*>(t->data_ptr<int64_t>()) : nullptr;
+}
 }  // namespace
 
 void logits_process(const at::Tensor& logits, const OptT& bias_ptr, const OptT& bias_idx,
                     const OptT& bias_val, const OptT& slot, const OptT& rp, const OptT& fp,
-                    const OptT& pp, const OptT& counts, at::Tensor& out) {
+                    const OptT& pp, const OptT& counts, at::Tensor& out, const OptT& g_table,
+                    const OptT& g_slot, const OptT& g_state) {
   need_cuda(logits, "logits");
   const int V = static_cast<int>(logits.size(-1));
   const int rows = static_cast<int>(logits.numel() / V);
   need_row_state(rows, V, bias_ptr, bias_idx, bias_val, slot, rp, fp, pp, counts);
   need_vec(out, at::kFloat, static_cast<int64_t>(rows) * V, "out");
+  need_guided(rows, g_table, g_slot, g_state);
   check(lumen_logits_process(dcode(logits), logits.data_ptr(), ptr<int>(bias_ptr),
                              ptr<int>(bias_idx), ptr<float>(bias_val), ptr<int>(slot),
                              ptr<float>(rp), ptr<float>(fp), ptr<float>(pp), ptr<int>(counts),
-                             counts ? static_cast<int>(counts->size(0)) : 0,
+                             counts ? static_cast<int>(counts->size(0)) : 0, llptr(g_table),
+                             ptr<int>(g_slot), ptr<int>(g_state),
+                             g_state ? static_cast<int>(g_state->numel()) : 0,
                              out.data_ptr<float>(), rows, V, cur_stream()),
         "logits_process");
 }
@@ -1193,7 +1212,8 @@ void sample_rows(const at::Tensor& logits, const at::Tensor& temperature,
                  const OptT& bias_ptr, const OptT& bias_idx, const OptT& bias_val,
                  const OptT& slot, const OptT& rp, const OptT& fp, const OptT& pp,
                  const OptT& counts, bool pre, at::Tensor& out_tokens, const OptT& out_logprob,
-                 const OptT& out_tau) {
+                 const OptT& out_tau, const OptT& g_table, const OptT& g_slot,
+                 const OptT& g_state) {
   need_cuda(logits, "logits");
   const int V = static_cast<int>(logits.size(-1));
   const int rows = static_cast<int>(logits.numel() / V);
@@ -1208,10 +1228,12 @@ void sample_rows(const at::Tensor& logits, const at::Tensor& temperature,
   need_vec(out_logprob, at::kFloat, rows, "out_logprob");
   need_vec(out_tau, at::kFloat, rows, "out_tau");
   need_row_state(rows, V, bias_ptr, bias_idx, bias_val, slot, rp, fp, pp, counts);
+  need_guided(rows, g_table, g_slot, g_state);
   at::Tensor lg = logits;
-  if (V > 32768 && !pre && (bias_ptr || (slot && counts))) {
+  if (V > 32768 && !pre && (bias_ptr || (slot && counts) || g_table)) {
     lg = at::empty({rows, V}, logits.options().dtype(at::kFloat));
-    logits_process(logits, bias_ptr, bias_idx, bias_val, slot, rp, fp, pp, counts, lg);
+    logits_process(logits, bias_ptr, bias_idx, bias_val, slot, rp, fp, pp, counts, lg, g_table,
+                   g_slot, g_state);
     pre = true;
   }
   check(lumen_sample_rows(
@@ -1221,7 +1243,8 @@ void sample_rows(const at::Tensor& logits, const at::Tensor& temperature,
             reinterpret_cast<const long long*>(rngrow.data_ptr<int64_t>()), ptr<float>(min_p),
             ptr<int>(bias_ptr), ptr<int>(bias_idx), ptr<float>(bias_val), ptr<int>(slot),
             ptr<float>(rp), ptr<float>(fp), ptr<float>(pp), ptr<int>(counts),
-            counts ? static_cast<int>(counts->size(0)) : 0, pre ? 1 : 0,
+            counts ? static_cast<int>(counts->size(0)) : 0, pre ? 1 : 0, llptr(g_table),
+            ptr<int>(g_slot), ptr<int>(g_state), g_state ? static_cast<int>(g_state->numel()) : 0,
             reinterpret_cast<long long*>(out_tokens.data_ptr<int64_t>()), ptr<float>(out_logprob),
             ptr<float>(out_tau), rows, V, cur_stream()),
         "sample_rows");
@@ -1539,11 +1562,14 @@ PYBIND11_MODULE(_C, m) {
         py::arg("slot") = py::none(), py::arg("rp") = py::none(), py::arg("fp") = py::none(),
         py::arg("pp") = py::none(), py::arg("counts") = py::none(), py::arg("pre") = false,
         py::arg("out_tokens"), py::arg("out_logprob") = py::none(),
-        py::arg("out_tau") = py::none());
+        py::arg("out_tau") = py::none(), py::arg("g_table") = py::none(),
+        py::arg("g_slot") = py::none(), py::arg("g_state") = py::none());
   m.def("logits_process", &logits_process, py::arg("logits"), py::arg("bias_ptr") = py::none(),
         py::arg("bias_idx") = py::none(), py::arg("bias_val") = py::none(),
         py::arg("slot") = py::none(), py::arg("rp") = py::none(), py::arg("fp") = py::none(),
-        py::arg("pp") = py::none(), py::arg("counts") = py::none(), py::arg("out"));
+        py::arg("pp") = py::none(), py::arg("counts") = py::none(), py::arg("out"),
+        py::arg("g_table") = py::none(), py::arg("g_slot") = py::none(),
+        py::arg("g_state") = py::none());
   m.def("sampler_state_init", &sampler_state_init);
   m.def("flash_attn", &flash_attn);
   m.def("flash_attn_paged", &flash_attn_paged);

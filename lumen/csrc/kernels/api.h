@@ -232,13 +232,15 @@ hipError_t lumen_sample_rows(int dtype, const void* logits, const float* tempera
                              const long long* offset, const long long* rngrow, const float* min_p,
                              const int* bias_ptr, const int* bias_idx, const float* bias_val,
                              const int* slot, const float* rp, const float* fp, const float* pp,
-                             int* counts, int S, int pre, long long* out_tok, float* out_lp,
-                             float* out_tau, int rows, int V, hipStream_t st);
+                             int* counts, int S, int pre, const long long* g_table,
+                             const int* g_slot, int* g_state, int G, long long* out_tok,
+                             float* out_lp, float* out_tau, int rows, int V, hipStream_t st);
 hipError_t lumen_logits_process(int dtype, const void* logits, const int* bias_ptr,
                                 const int* bias_idx, const float* bias_val, const int* slot,
                                 const float* rp, const float* fp, const float* pp,
-                                const int* counts, int S, float* out, int rows, int V,
-                                hipStream_t st);
+                                const int* counts, int S, const long long* g_table,
+                                const int* g_slot, const int* g_state, int G, float* out,
+                                int rows, int V, hipStream_t st);
 hipError_t lumen_sampler_state_init(int* counts, const int* slots, const int* ptr,
                                     const int* n_prompt, const int* ids, int n, int S, int V,
                                     hipStream_t st);

@@ -3,6 +3,12 @@
 //
 // Reference behaviour: vLLM 0.6.0's logits processors and Sampler, in its order.  With x the f32
 // logits of a sampled row:
+//   0. guided decoding: a row with a token table (int16 next[S][V] of its grammar, the device
+//      address in g_table, 0 = unguided) and st = g_state[g_slot[row]]: x[j] = -inf where
+//      next[st][j] < 0.  -inf stays -inf through the steps below, has the lowest radix key, no
+//      top-p mass and never wins the draw, so out_lp is the log-probability under the masked
+//      distribution.  After the draw thread 0 stores next[st][token] into g_state when it is
+//      >= 0 (one row per slot per step, as for the counts)
 //   1. logit_bias (sparse CSR list per row): x[j] += bias (the bias may be -inf; the engine also
 //      lowers min_tokens to -inf entries for EOS / the stop ids)
 //   2. penalties from the sequence's count row c[j] (int32: bit 31 = "in the prompt", bits 0..30
@@ -60,6 +66,22 @@ __device__ __forceinline__ void penalize_row(float* x, const int* __restrict__ c
     x[j] = penalize(x[j], cnt[j], rp, fp, pp) * scale;
 }
 
+// x[j] = -inf where the grammar's table row forbids token j; 8 entries a load when aligned
+// (V % 8 != 0 leaves every second state row unaligned)
+__device__ __forceinline__ void mask_row(float* x, const short* __restrict__ nx, int V) {
+  const bool al = (reinterpret_cast<uintptr_t>(nx) & 15) == 0;
+  const int nv = al ? V / 8 : 0;
+  for (int i = threadIdx.x; i < nv; i += blockDim.x) {
+    const uint4 u = reinterpret_cast<const uint4*>(nx)[i];
+    const short* e = reinterpret_cast<const short*>(&u);
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+      if (e[t] < 0) x[i * 8 + t] = -INFINITY;
+  }
+  for (int j = nv * 8 + threadIdx.x; j < V; j += blockDim.x)
+    if (nx[j] < 0) x[j] = -INFINITY;
+}
+
 struct RowArgs {
   const long long* seed;    // [R]
   const long long* offset;  // [R]
@@ -74,8 +96,25 @@ struct RowArgs {
   const float* pp;
   int* counts;              // [S, V] or null
   int S;
-  int pre;                  // logits already hold the processed x: only the count update is left
+  int pre;                  // logits already hold the processed x: only the state updates are left
+  const long long* g_table; // [R] device address of the row's int16 next[S][V], 0 = unguided; or null
+  const int* g_slot;        // [R]
+  int* g_state;             // [G] automaton state per slot
+  int G;
 };
+
+// the table row of this logits row's automaton state (null: unguided); *gslot = its state slot
+__device__ __forceinline__ const short* guided_row(const RowArgs& a, int row_i, int V,
+                                                   int* gslot) {
+  if (!a.g_table || !a.g_slot || !a.g_state) return nullptr;
+  const long long addr = a.g_table[row_i];
+  const int gs = a.g_slot[row_i];
+  if (addr == 0 || gs < 0 || gs >= a.G) return nullptr;
+  const int st = a.g_state[gs];
+  if (st < 0) return nullptr;
+  *gslot = gs;
+  return reinterpret_cast<const short*>(addr) + static_cast<size_t>(st) * V;
+}
 
 template <typename T, int NPT>
 __global__ void __launch_bounds__(kSampNT) sample_rows_kernel(
@@ -101,11 +140,14 @@ __global__ void __launch_bounds__(kSampNT) sample_rows_kernel(
   row.zl = zlds;
   int slot = (a.slot && a.counts) ? a.slot[row_i] : -1;
   if (slot >= a.S) slot = -1;
+  int gslot = -1;
+  const short* gt = guided_row(a, row_i, V, &gslot);  // uniform over the workgroup
   if constexpr (NPT > 0) {
     const int b0 = (a.bias_ptr && !a.pre) ? a.bias_ptr[row_i] : 0;
     const int b1 = (a.bias_ptr && !a.pre) ? a.bias_ptr[row_i + 1] : 0;
     const bool pen = slot >= 0 && !a.pre;
-    const bool proc = pen || b1 > b0;  // uniform over the workgroup
+    const bool msk = gt != nullptr && !a.pre;
+    const bool proc = pen || b1 > b0 || msk;  // uniform over the workgroup
     // the fill of sampling.hip; a processed row is filled unscaled and scaled after step 2
     const float fs = proc ? 1.f : row.invT;
     constexpr int E = 16 / static_cast<int>(sizeof(T));
@@ -131,6 +173,10 @@ __global__ void __launch_bounds__(kSampNT) sample_rows_kernel(
     for (int j = nv * E + threadIdx.x; j < V; j += kSampNT) zlds[j] = to_f32(row.p[j]) * fs;
     __syncthreads();
     if (proc) {
+      if (msk) {
+        mask_row(zlds, gt, V);
+        __syncthreads();
+      }
       if (b1 > b0) {
         add_bias(zlds, V, a.bias_idx, a.bias_val, b0, b1);
         __syncthreads();
@@ -232,6 +278,10 @@ __global__ void __launch_bounds__(kSampNT) sample_rows_kernel(
       int* c = a.counts + static_cast<size_t>(slot) * V + idx;
       *c = *c + 1;
     }
+    if (gt) {
+      const int n = gt[idx];
+      if (n >= 0) a.g_state[gslot] = n;
+    }
   }
 }
 
@@ -242,7 +292,13 @@ __global__ void __launch_bounds__(kSampNT) logits_process_kernel(
   const int row_i = blockIdx.x;
   const T* p = logits + static_cast<size_t>(row_i) * V;
   float* x = out + static_cast<size_t>(row_i) * V;
-  for (int j = threadIdx.x; j < V; j += kSampNT) x[j] = to_f32(p[j]);
+  int gslot = -1;
+  const short* gt = guided_row(a, row_i, V, &gslot);
+  if (gt) {
+    for (int j = threadIdx.x; j < V; j += kSampNT) x[j] = gt[j] < 0 ? -INFINITY : to_f32(p[j]);
+  } else {
+    for (int j = threadIdx.x; j < V; j += kSampNT) x[j] = to_f32(p[j]);
+  }
   int slot = (a.slot && a.counts) ? a.slot[row_i] : -1;
   if (slot >= a.S) slot = -1;
   const int b0 = a.bias_ptr ? a.bias_ptr[row_i] : 0;
@@ -314,21 +370,23 @@ hipError_t launch_sample_rows(const void* logits, const float* temperature, cons
 
 // The fused path.  For V > 32768 the kernel applies neither bias nor penalties: the caller
 // passes processed f32 logits (lumen_logits_process) with pre = 1.  counts may be null (no
-// state): slot is then ignored.  out_tau as in lumen_sample.
+// state): slot is then ignored.  g_table / g_slot / g_state (all three or none) guide rows; with
+// pre = 1 the mask is not applied again and the state still advances.  out_tau as in lumen_sample.
 extern "C" hipError_t lumen_sample_rows(
     int dtype, const void* logits, const float* temperature, const float* top_p,
     const int* top_k, const long long* seed, const long long* offset, const long long* rngrow,
     const float* min_p, const int* bias_ptr, const int* bias_idx, const float* bias_val,
     const int* slot, const float* rp, const float* fp, const float* pp, int* counts, int S,
-    int pre, long long* out_tok, float* out_lp, float* out_tau, int rows, int V,
-    hipStream_t st) {
+    int pre, const long long* g_table, const int* g_slot, int* g_state, int G,
+    long long* out_tok, float* out_lp, float* out_tau, int rows, int V, hipStream_t st) {
   if (rows == 0) return hipSuccess;
   if (V < 1 || !seed || !offset || !rngrow) return hipErrorInvalidValue;
   if (counts && slot && !pre && (!rp || !fp || !pp)) return hipErrorInvalidValue;
-  if (V > lumen::kSampLdsV && !pre && (bias_ptr || (counts && slot)))
+  if (g_table && (!g_slot || !g_state || G < 1)) return hipErrorInvalidValue;
+  if (V > lumen::kSampLdsV && !pre && (bias_ptr || (counts && slot) || g_table))
     return hipErrorInvalidValue;  // the no-LDS form samples processed logits only
   const lumen::RowArgs a{seed, offset, rngrow, min_p, bias_ptr, bias_idx, bias_val, slot,
-                         rp, fp, pp, counts, S, pre};
+                         rp, fp, pp, counts, S, pre, g_table, g_slot, g_state, G};
   if (dtype == lumen::kF32)
     return lumen::launch_sample_rows<float>(logits, temperature, top_p, top_k, a, out_tok,
                                             out_lp, out_tau, rows, V, st);
@@ -344,12 +402,15 @@ extern "C" hipError_t lumen_sample_rows(
 extern "C" hipError_t lumen_logits_process(
     int dtype, const void* logits, const int* bias_ptr, const int* bias_idx,
     const float* bias_val, const int* slot, const float* rp, const float* fp, const float* pp,
-    const int* counts, int S, float* out, int rows, int V, hipStream_t st) {
+    const int* counts, int S, const long long* g_table, const int* g_slot, const int* g_state,
+    int G, float* out, int rows, int V, hipStream_t st) {
   if (rows == 0) return hipSuccess;
   if (V < 1) return hipErrorInvalidValue;
   if (counts && slot && (!rp || !fp || !pp)) return hipErrorInvalidValue;
+  if (g_table && (!g_slot || !g_state || G < 1)) return hipErrorInvalidValue;
   const lumen::RowArgs a{nullptr, nullptr, nullptr, nullptr, bias_ptr, bias_idx, bias_val, slot,
-                         rp, fp, pp, const_cast<int*>(counts), S, 0};
+                         rp, fp, pp, const_cast<int*>(counts), S, 0, g_table, g_slot,
+                         const_cast<int*>(g_state), G};
   dim3 grid(rows), block(lumen::kSampNT);
   if (dtype == lumen::kF32)
     hipLaunchKernelGGL((lumen::logits_process_kernel<float>), grid, block, 0, st,

@@ -54,6 +54,8 @@ class _Stats:
         self.errors = 0
         self.prompt_tokens = 0
         self.completion_tokens = 0
+        self.guided_requests = 0
+        self.guided_compile_seconds = 0.0
         self.ttft: List[float] = []
         self.itl: List[float] = []
 
@@ -75,8 +77,26 @@ def _quantiles(xs, qs=(0.5, 0.9, 0.99)):
     return {q: s[min(len(s) - 1, int(q * len(s)))] for q in qs}
 
 
-def _params(body: Dict[str, Any], eos: Optional[int]) -> SamplingParams:
+def _guided(body: Dict[str, Any], max_states: int):
+    """(guided, guided_dfa, compile seconds) of a request body: the grammar is compiled here, in the API process,
+    so whatever the compiler rejects is a 400 before the request reaches the engine core, which
+    receives the automaton and only builds the token table."""
+    from .guided import compile_guided, parse_guided_fields
+
+    g = parse_guided_fields(body)
+    if g is None:
+        return None, None, 0.0
+    gr = compile_guided(g[0], g[1], max_states)
+    spent, gr.compile_seconds = gr.compile_seconds, 0.0   # counted once: repeats hit the cache
+    return g, (gr.trans, gr.accept), spent
+
+
+def _params(body: Dict[str, Any], eos: Optional[int], max_states: int = 4096,
+            stats=None) -> SamplingParams:
     stop_ids = body.get("stop_token_ids") or []
+    guided, dfa, spent = _guided(body, max_states)
+    if stats is not None:
+        stats.guided_compile_seconds += spent
     bias = body.get("logit_bias")
     if bias is not None:
         # OpenAI's JSON shape: {"<token id>": bias}
@@ -86,16 +106,20 @@ def _params(body: Dict[str, Any], eos: Optional[int]) -> SamplingParams:
             bias = {int(k): float(v) for k, v in bias.items()}
         except (TypeError, ValueError):
             raise ValueError("logit_bias keys must be token ids and its values numbers")
-    return SamplingParams(max_tokens=int(body.get("max_tokens") or 16),
-                          temperature=float(body.get("temperature", 1.0)),
-                          top_p=float(body.get("top_p", 1.0)), top_k=int(body.get("top_k", 0) or 0),
-                          stop_token_ids=list(stop_ids), ignore_eos=bool(body.get("ignore_eos", False)),
-                          seed=body.get("seed"),
-                          presence_penalty=float(body.get("presence_penalty") or 0.0),
-                          frequency_penalty=float(body.get("frequency_penalty") or 0.0),
-                          repetition_penalty=float(body.get("repetition_penalty") or 1.0),
-                          min_p=float(body.get("min_p") or 0.0), logit_bias=bias or None,
-                          min_tokens=int(body.get("min_tokens") or 0))
+    params = SamplingParams(
+        max_tokens=int(body.get("max_tokens") or 16),
+        temperature=float(body.get("temperature", 1.0)),
+        top_p=float(body.get("top_p", 1.0)), top_k=int(body.get("top_k", 0) or 0),
+        stop_token_ids=list(stop_ids), ignore_eos=bool(body.get("ignore_eos", False)),
+        seed=body.get("seed"),
+        presence_penalty=float(body.get("presence_penalty") or 0.0),
+        frequency_penalty=float(body.get("frequency_penalty") or 0.0),
+        repetition_penalty=float(body.get("repetition_penalty") or 1.0),
+        min_p=float(body.get("min_p") or 0.0), logit_bias=bias or None,
+        min_tokens=int(body.get("min_tokens") or 0), guided=guided, guided_dfa=dfa)
+    if stats is not None and guided is not None:
+        stats.guided_requests += 1
+    return params
 
 
 def _logprob_request(body: Dict[str, Any], chat: bool, params: SamplingParams) -> bool:
@@ -321,6 +345,7 @@ def create_app(aengine, served_model_name: Optional[str] = None):
         return {"prompt": decode(ids)}
 
     loras = list(getattr(aengine, "lora_names", []) or [])
+    gmax = int(getattr(aengine, "guided_max_states", 4096))
 
     @app.get("/v1/models")
     async def models():
@@ -352,6 +377,13 @@ def create_app(aengine, served_model_name: Optional[str] = None):
             f"lumen_preemptions_total {live['preemptions']}",
             "# TYPE lumen_prefix_cache_hit_ratio gauge",
             f"lumen_prefix_cache_hit_ratio {live.get('prefix_hit_rate', 0.0):.4f}",
+            "# TYPE lumen_guided_requests_total counter",
+            f"lumen_guided_requests_total {stats.guided_requests}",
+            "# TYPE lumen_guided_cache_hits_total counter",
+            f"lumen_guided_cache_hits_total {live.get('guided_cache_hits', 0)}",
+            "# TYPE lumen_guided_compile_seconds_total counter",
+            "lumen_guided_compile_seconds_total %.6f"
+            % (stats.guided_compile_seconds + live.get("guided_compile_seconds", 0.0)),
         ]
         return PlainTextResponse("\n".join(lines) + "\n")
 
@@ -558,7 +590,7 @@ def create_app(aengine, served_model_name: Optional[str] = None):
                 raise HTTPException(status_code=400, detail="batched string prompts: send one per request")
             prompt = prompt[0]
         try:
-            params = _params(body, aengine.eos_id)
+            params = _params(body, aengine.eos_id, gmax, stats)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
         return await _run(prompt, params, False, bool(body.get("stream", False)),
@@ -571,7 +603,7 @@ def create_app(aengine, served_model_name: Optional[str] = None):
         if not msgs:
             raise HTTPException(status_code=400, detail="messages required")
         try:
-            params = _params(body, aengine.eos_id)
+            params = _params(body, aengine.eos_id, gmax, stats)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e))
         return await _run(llama2_chat_prompt(msgs), params, True, bool(body.get("stream", False)),

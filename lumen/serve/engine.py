@@ -25,7 +25,8 @@ from ..models import build_model, get_config
 from .block_manager import BlockManager
 from .model_runner import (ModelRunner, ServeWeights, StepInput, kv_bytes_per_token,
                            process_logits_ref, sample_rows_ref)
-from .sampler_state import RowParams, SamplerState, bias_csr, counts_from_ids
+from .sampler_state import (GuidedState, RowParams, SamplerState, advance_guided_ref, bias_csr,
+                            counts_from_ids)
 from .scheduler import Batch, Scheduler, SchedulerConfig
 from .sequence import SamplingParams, Sequence, Status
 
@@ -93,6 +94,11 @@ class EngineConfig:
     # (int keys, pruned as the window slides): at most ngram_window * (ngram_max - ngram_min + 1)
     # dict entries per sequence -- 4 * 1024 with the defaults, ~0.4 MB; 256 sequences ~100 MB
     ngram_window: int = 1024
+    # guided decoding (lumen/serve/guided.py): a grammar may have at most this many automaton
+    # states (its token table is states * V * 2 bytes: 262 MB at 4096 x 32000), and the engine
+    # keeps compiled tables up to this many MB (LRU; a table in use is never evicted)
+    guided_max_states: int = 4096
+    guided_cache_mb: int = 1024
 
 
 _DT = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
@@ -254,7 +260,20 @@ class LLMEngine:
                           and os.environ.get("LUMEN_DISABLE_NATIVE", "0") != "1"
                           and os.environ.get("LUMEN_SAMPLER_STATE", "1") != "0")
         self.sampler_state = SamplerState(cfg.max_num_seqs, self.model_config.vocab_size, dev)
-        self.scheduler.on_release = self.sampler_state.release
+        # guided decoding: the automaton state of the running guided sequences, next to the
+        # counts; token tables are compiled per grammar and cached (guided.GuidedCache)
+        from .guided import GuidedCache
+        self.guided_state = GuidedState(cfg.max_num_seqs, dev)
+        self.guided_cache = GuidedCache(int(cfg.guided_cache_mb) << 20)
+        self._token_bytes = None
+        self.guided_requests = 0
+
+        def on_release(seq):
+            self.sampler_state.release(seq)
+            self.guided_state.release(seq)
+            if seq.finished:
+                self.guided_cache.evict()
+        self.scheduler.on_release = on_release
         self.stats = {"prefill_tokens": 0, "decode_tokens": 0, "steps": 0, "requests": 0,
                       "finished": 0, "overlapped_steps": 0, "spec_proposed": 0,
                       "spec_accepted": 0, "spec_steps": 0}
@@ -306,7 +325,12 @@ class LLMEngine:
             if bad:
                 raise ValueError(f"logit_bias token id {bad[0]} is outside the vocabulary "
                                  f"(0..{V - 1})")
+        table = self._guided_table(params) if params.guided is not None else None
         seq = Sequence(ids, params, request_id or uuid.uuid4().hex)
+        if table is not None:
+            seq.guided_table = table
+            table.refs += 1
+            self.guided_requests += 1
         if lora:
             if self.runner.lora is None or lora not in self.lora_names:
                 raise ValueError(f"unknown LoRA adapter '{lora}' (serving: {self.lora_names})")
@@ -314,6 +338,64 @@ class LLMEngine:
         self.scheduler.add(seq)
         self.stats["requests"] += 1
         return seq
+
+    def token_bytes(self):
+        if self._token_bytes is None:
+            from .guided import token_bytes
+            self._token_bytes = token_bytes(self.tokenizer)
+        return self._token_bytes
+
+    def _guided_table(self, params: SamplingParams):
+        """The token table of the request's grammar, from the cache or built now (on the
+        engine's device).  ``ValueError`` for what the compiler rejects."""
+        from .guided import (Grammar, TokenTable, build_token_index, compile_guided,
+                             guided_digest, tokenizer_identity)
+
+        kind, payload = params.guided
+        if self.eos_id is None:
+            raise ValueError("guided decoding needs a tokenizer with an EOS token")
+        key = guided_digest(kind, payload) + "|" + tokenizer_identity(self.tokenizer)
+        cap = int(self.cfg.guided_max_states)
+
+        def build():
+            if params.guided_dfa is not None:
+                trans, accept = params.guided_dfa
+                g = Grammar(kind, payload, np.asarray(trans, dtype=np.int32),
+                            np.asarray(accept, dtype=bool))
+            else:
+                g = compile_guided(kind, payload, cap)
+            if g.num_states > cap:
+                raise ValueError(f"grammar needs {g.num_states} states, more than the limit of "
+                                 f"{cap} (--guided-max-states)")
+            nxt, live = build_token_index(g.trans, g.accept, self.token_bytes(),
+                                          self.model_config.vocab_size, self.eos_id, self.device)
+            return TokenTable(g, nxt, live)
+
+        table = self.guided_cache.get(key, build)
+        params.guided_dfa = None     # the table holds the grammar; requests need not carry it
+        return table
+
+    def guided_stats(self) -> dict:
+        c = self.guided_cache
+        return {"guided_requests": self.guided_requests, "guided_cache_hits": c.hits,
+                "guided_compile_seconds": c.compile_seconds, "guided_cache_bytes": c.nbytes}
+
+    def _guided_resume_state(self, s: Sequence) -> int:
+        """The automaton state of a sequence that is sampled for the first time or again after a
+        preemption: its host output ids walked through the grammar with the token bytes."""
+        if not s.output_ids:
+            return 0
+        g = s.guided_table.grammar
+        tb = self.token_bytes()
+        st = 0
+        for t in s.output_ids:
+            b = tb[t] if 0 <= t < len(tb) else None
+            if b is None:
+                continue             # EOS / a special token leaves the state alone
+            n = g.walk(b, st)
+            if n >= 0:
+                st = n
+        return st
 
     def abort(self, request_id: str) -> None:
         self.scheduler.abort(request_id)
@@ -520,6 +602,22 @@ class LLMEngine:
                     new.append(s)
         slot = np.fromiter((-1 if (verify and i < Tp) else s.state_slot
                             for i, s in enumerate(rseqs)), np.int64, R)
+        # guided rows: the table's address and the sequence's automaton-state slot (verify rows
+        # of a drafted chunk carry none: _propose drafts no guided sequence)
+        gnew = []
+        guided = any(s.guided_table is not None for s in rseqs)
+        if guided:
+            gs = self.guided_state
+            for i, s in enumerate(rseqs):
+                if s.guided_table is not None and s.guided_slot < 0 and not (verify and i < Tp):
+                    s.guided_slot = gs.acquire()
+                    gnew.append(s)
+            grow = [s.guided_table is not None and not (verify and i < Tp)
+                    for i, s in enumerate(rseqs)]
+            gaddr = np.fromiter((s.guided_table.address if g else 0
+                                 for g, s in zip(grow, rseqs)), np.int64, R)
+            gslot = np.fromiter((s.guided_slot if g else -1 for g, s in zip(grow, rseqs)),
+                                np.int64, R)
         f4 = np.concatenate([np.fromiter((p.min_p for p in ps), np.float64, R),
                              np.fromiter((p.repetition_penalty for p in ps), np.float64, R),
                              np.fromiter((p.frequency_penalty for p in ps), np.float64, R),
@@ -531,6 +629,11 @@ class LLMEngine:
         pack = [seed, offset, rngrow, f4.view(np.int64), slot]
         if nb:
             pack += [bptr, bidx, bval.view(np.int64)]
+        if guided:
+            pack += [gaddr, gslot,
+                     np.fromiter((s.guided_slot for s in gnew), np.int64, len(gnew)),
+                     np.fromiter((self._guided_resume_state(s) for s in gnew), np.int64,
+                                 len(gnew))]
         n_ids = 0
         if new:
             lens = np.fromiter((len(s.prompt_ids) + len(s.output_ids) for s in new), np.int64,
@@ -543,7 +646,11 @@ class LLMEngine:
             pack += [np.asarray(s.prompt_ids + s.output_ids, dtype=np.int64) for s in new]
         host = {"seeds": [p.seed for p in ps], "offsets": offset, "bias": bias, "seqs": rseqs,
                 "min_p": f4[:R], "rp": f4[R:2 * R], "fp": f4[2 * R:3 * R], "pp": f4[3 * R:]}
-        return {"pack": pack, "nb": nb, "new": len(new), "n_ids": n_ids, "host": host}
+        if guided:
+            host["g_tables"] = [s.guided_table.next if g else None for g, s in zip(grow, rseqs)]
+            host["g_slots"] = gslot
+        return {"pack": pack, "nb": nb, "new": len(new), "n_ids": n_ids, "host": host,
+                "guided": guided, "gnew": len(gnew)}
 
     @staticmethod
     def _unpack_row_params(inp: StepInput, rowp: dict, dev: torch.Tensor, o: int, R: int) -> int:
@@ -562,6 +669,13 @@ class LLMEngine:
             sp.bias_ptr, sp.bias_idx = ints[R:2 * R + 1], ints[2 * R + 1:]
             sp.bias_val = dev[o:o + nb].view(torch.float64).float()
             o += nb
+        if rowp["guided"]:
+            gn = rowp["gnew"]
+            sp.g_table, sp.g_slot = dev[o:o + R], dev[o + R:o + 2 * R].int()
+            o += 2 * R
+            if gn:
+                sp.host["g_init"] = (dev[o:o + gn], dev[o + gn:o + 2 * gn].int())
+                o += 2 * gn
         if n:
             init = dev[o:o + 3 * n + 1 + n_ids].int()
             o += 3 * n + 1 + n_ids
@@ -588,6 +702,12 @@ class LLMEngine:
                                        self.step_count, want_logprobs=True)
             return t, lp, logits
         h = sp.host
+        gstate = None
+        if sp.g_table is not None:
+            # newly admitted guided sequences: their automaton state, before this step's launch
+            if "g_init" in h:
+                self.guided_state.write(*h.pop("g_init"))
+            gstate = self.guided_state.state
         if not (logits.is_cuda and self._native_rows(logits)):
             counts = None
             if host_pen:
@@ -595,9 +715,16 @@ class LLMEngine:
                 counts = torch.stack([
                     counts_from_ids(s.prompt_ids, s.output_ids, V) if s.params.has_penalties
                     else torch.zeros(V, dtype=torch.int64) for s in rseqs])
-            x = process_logits_ref(logits, counts, h["rp"], h["fp"], h["pp"], bias=h["bias"])
+            mask = None
+            if gstate is not None:
+                mask = [None if nx is None else nx[int(gstate[int(h["g_slots"][i])])] < 0
+                        for i, nx in enumerate(h["g_tables"])]
+            x = process_logits_ref(logits, counts, h["rp"], h["fp"], h["pp"], bias=h["bias"],
+                                   mask=mask)
             t, lp = sample_rows_ref(x, inp.temps, inp.top_ps, inp.top_ks, h["min_p"],
                                     h["seeds"], h["offsets"], self.cfg.seed, self.step_count)
+            if gstate is not None:
+                advance_guided_ref(gstate, h["g_tables"], h["g_slots"], t)
             return t, lp, x
         counts = None
         if "init" in h:
@@ -607,13 +734,13 @@ class LLMEngine:
         pre = False
         if host_pen:
             # LUMEN_SAMPLER_STATE=0: the bias on the device, then the host-side penalties
-            logits = apply_penalties(self.runner.logits_process(logits, sp), rseqs)
+            logits = apply_penalties(self.runner.logits_process(logits, sp, gstate=gstate), rseqs)
             pre = True
         elif want_x:
-            logits = self.runner.logits_process(logits, sp, counts)
+            logits = self.runner.logits_process(logits, sp, counts, gstate=gstate)
             pre = True
         t, lp = self.runner.sample_rows(logits, inp.temps, inp.top_ps, inp.top_ks, sp, counts,
-                                        pre=pre, want_logprobs=True)
+                                        pre=pre, want_logprobs=True, gstate=gstate)
         return t, lp, logits
 
     @staticmethod
@@ -850,8 +977,8 @@ class LLMEngine:
             p = s.params
             if p.temperature > 0 or p.has_penalties or p.wants_extras:
                 continue
-            if p.logit_bias or s.num_generated < p.min_tokens:
-                continue                      # drafted rows carry no bias and no bans
+            if p.logit_bias or s.num_generated < p.min_tokens or p.guided is not None:
+                continue                      # drafted rows carry no bias, no bans and no mask
             if s.spec_wait > 0:
                 s.spec_wait -= 1
                 continue
@@ -949,7 +1076,9 @@ class LLMEngine:
             z = torch.where(t > 0, z / t.clamp(min=1e-6), z)
             v, ix = torch.log_softmax(z, -1).topk(max(ks), -1)
             v, ix = v.tolist(), ix.tolist()
-            tops = [list(zip(ix[i][:k], v[i][:k])) if k else None for i, k in enumerate(ks)]
+            # a guided row's masked tokens (logprob -inf) are no alternatives
+            tops = [[(j, x) for j, x in zip(ix[i][:k], v[i][:k]) if x != float("-inf")] if k
+                    else None for i, k in enumerate(ks)]
         meta = inp.prompt_meta
         if meta:
             lp = torch.log_softmax(self.runner.extra_logits.float(), -1)
@@ -1046,7 +1175,11 @@ class AsyncEngine:
         sch = self.engine.scheduler
         return {"kv_usage": self.engine.blocks.usage(), "running": len(sch.running),
                 "waiting": len(sch.waiting), "preemptions": sch.num_preemptions,
-                "prefix_hit_rate": self.engine.blocks.hit_rate}
+                "prefix_hit_rate": self.engine.blocks.hit_rate, **self.engine.guided_stats()}
+
+    @property
+    def guided_max_states(self) -> int:
+        return self.engine.cfg.guided_max_states
 
     def _push(self, rid, item):
         st = self._streams.get(rid)

@@ -112,7 +112,7 @@ def run_engine_core(engine, req_q, out_q, idle_sleep: float = 0.0005) -> None:
             sch = engine.scheduler
             stats = {"kv_usage": engine.blocks.usage(), "running": len(sch.running),
                      "waiting": len(sch.waiting), "preemptions": sch.num_preemptions,
-                     "prefix_hit_rate": engine.blocks.hit_rate}
+                     "prefix_hit_rate": engine.blocks.hit_rate, **engine.guided_stats()}
             for o, ups in updates.items():
                 outs[o].put(("step", ups, stats))
 
@@ -149,8 +149,10 @@ class EngineCoreClient:
     engine core in another process."""
 
     def __init__(self, req_q, out_q, tokenizer, model_name: str, max_model_len: int,
-                 eos_id: Optional[int], lora_names: Optional[List[str]] = None, index: int = 0):
+                 eos_id: Optional[int], lora_names: Optional[List[str]] = None, index: int = 0,
+                 guided_max_states: int = 4096):
         self.req_q, self.out_q = req_q, out_q
+        self.guided_max_states = guided_max_states   # grammars are compiled and checked here
         self.index = index  # which of the core's output queues carries this front-end's tokens
         self.lora_names = list(lora_names or [])
         self.tokenizer = tokenizer
@@ -238,7 +240,7 @@ def _deliver(items):
 def api_process_main(req_q, out_q, model: str, max_model_len: int, host: str, port: int,
                      served_model_name: Optional[str], vocab_size: int,
                      lora_names: Optional[List[str]] = None, index: int = 0,
-                     reuse_port: bool = False) -> None:
+                     reuse_port: bool = False, guided_max_states: int = 4096) -> None:
     """Entry point of a spawned HTTP process (no GPU).  ``reuse_port``: one of several API
     processes listening on the same port (SO_REUSEPORT)."""
     import os
@@ -260,7 +262,7 @@ def api_process_main(req_q, out_q, model: str, max_model_len: int, host: str, po
     tok = load_tokenizer(model, vocab_size)
     eos = getattr(tok, "eos_token_id", None)
     client = EngineCoreClient(req_q, out_q, tok, served_model_name or model, max_model_len, eos,
-                              lora_names, index)
+                              lora_names, index, guided_max_states)
     app = create_app(client, served_model_name)
     if not reuse_port:
         uvicorn.run(app, host=host, port=port, log_level="warning")
@@ -277,7 +279,7 @@ def api_process_main(req_q, out_q, model: str, max_model_len: int, host: str, po
 
 def start_api_servers(count: int, model: str, max_model_len: int, host: str, port: int,
                       served_model_name: Optional[str], vocab_size: int,
-                      lora_names: Optional[List[str]] = None):
+                      lora_names: Optional[List[str]] = None, guided_max_states: int = 4096):
     """Spawn ``count`` API processes on ``host:port`` sharing one request queue; returns
     (request queue, [output queue per process], [processes]) for ``run_engine_core``."""
     import multiprocessing as mp
@@ -289,7 +291,8 @@ def start_api_servers(count: int, model: str, max_model_len: int, host: str, por
         out_q = ctx.Queue()
         p = ctx.Process(target=api_process_main, name=f"lumen-api{i}",
                         args=(req_q, out_q, model, max_model_len, host, port, served_model_name,
-                              vocab_size, lora_names, i, count > 1), daemon=True)
+                              vocab_size, lora_names, i, count > 1, guided_max_states),
+                        daemon=True)
         p.start()
         out_qs.append(out_q)
         procs.append(p)

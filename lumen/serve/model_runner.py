@@ -533,20 +533,23 @@ class ModelRunner:
         return sample_ref(logits, t, p, k, seed, offset)
 
     @torch.no_grad()
-    def logits_process(self, logits: torch.Tensor, sp, counts: Optional[torch.Tensor] = None):
-        """The processed f32 logits of the sampled rows (logit_bias, then the penalties from
-        ``counts``): what ``sample_rows`` draws from, materialised."""
+    def logits_process(self, logits: torch.Tensor, sp, counts: Optional[torch.Tensor] = None,
+                       gstate: Optional[torch.Tensor] = None):
+        """The processed f32 logits of the sampled rows (the grammar mask of guided rows from
+        ``gstate``, logit_bias, then the penalties from ``counts``): what ``sample_rows`` draws
+        from, materialised."""
         out = torch.empty(logits.shape, dtype=torch.float32, device=logits.device)
         st = counts is not None
         native().logits_process(logits.contiguous(), sp.bias_ptr, sp.bias_idx, sp.bias_val,
                                 sp.slot if st else None, sp.rp if st else None,
-                                sp.fp if st else None, sp.pp if st else None, counts, out)
+                                sp.fp if st else None, sp.pp if st else None, counts, out,
+                                **_guided_args(sp, gstate))
         return out
 
     @torch.no_grad()
     def sample_rows(self, logits: torch.Tensor, temps, top_ps, top_ks, sp,
                     counts: Optional[torch.Tensor] = None, pre: bool = False,
-                    want_logprobs: bool = True):
+                    want_logprobs: bool = True, gstate: Optional[torch.Tensor] = None):
         """The per-row sampler entry (kernels/sampling_rows.hip): ``sp`` is a RowParams of device
         tensors.  ``pre``: the logits are ``logits_process`` output already (the sampled tokens'
         counts still advance)."""
@@ -558,8 +561,16 @@ class ModelRunner:
         native().sample_rows(logits.contiguous(), temps, top_ps, top_ks, sp.seed, sp.offset,
                              sp.rngrow, sp.min_p, sp.bias_ptr, sp.bias_idx, sp.bias_val,
                              sp.slot if st else None, sp.rp if st else None,
-                             sp.fp if st else None, sp.pp if st else None, counts, pre, out, lp)
+                             sp.fp if st else None, sp.pp if st else None, counts, pre, out, lp,
+                             **_guided_args(sp, gstate))
         return out, lp
+
+
+def _guided_args(sp, gstate) -> dict:
+    """The guided-decoding keywords of the per-row entries (none for a step without one)."""
+    if gstate is None or getattr(sp, "g_table", None) is None:
+        return {}
+    return {"g_table": sp.g_table, "g_slot": sp.g_slot, "g_state": gstate}
 
 
 def topk_topp_keep(zs: torch.Tensor, k: int, p: float) -> torch.Tensor:
@@ -604,14 +615,19 @@ def sample_ref(logits, temps, top_ps, top_ks, seed, offset):
     return out, lps
 
 
-def process_logits_ref(logits, counts=None, rp=None, fp=None, pp=None, bias=None):
+def process_logits_ref(logits, counts=None, rp=None, fp=None, pp=None, bias=None, mask=None):
     """Torch reference of steps 1-3 of the per-row sampler (kernels/sampling_rows.hip), in
     ``logits.float()`` precision (pass f64 logits for an f64 reference): ``bias`` is a list of
     (idx, val) pairs per row or None; ``counts`` [R, V] integer rows (bit 31 = in the prompt,
     bits 0..30 = times generated; an all-zero row = no state).  logit_bias first, then the
-    repetition penalty on the biased logit's sign, then frequency / presence."""
+    repetition penalty on the biased logit's sign, then frequency / presence.  ``mask``: per
+    row None or a bool [V] of the tokens a grammar forbids (-inf before everything else)."""
     x = logits.clone() if logits.dtype == torch.float64 else logits.float().clone()
     R, V = x.shape
+    if mask is not None:
+        for i, m in enumerate(mask):
+            if m is not None:
+                x[i, torch.as_tensor(m, dtype=torch.bool, device=x.device)] = -float("inf")
     if bias is not None:
         for i, e in enumerate(bias):
             if e is None:

@@ -34,6 +34,8 @@ class RowParams:
     bias_ptr: Optional[object] = None   # CSR over the rows, int32 [R + 1] (None: no entries)
     bias_idx: Optional[object] = None   # int32
     bias_val: Optional[object] = None   # f32 (-inf: banned)
+    g_table: Optional[object] = None    # [R] int64 address of the row's token table, 0 = unguided
+    g_slot: Optional[object] = None     # [R] int32 row of GuidedState.state
     host: dict = field(default_factory=dict)   # the same arrays as numpy (CPU reference path)
 
 
@@ -72,6 +74,52 @@ class SamplerState:
         from ..ops._native import native
 
         native().sampler_state_init(self.counts, slots, ptr, n_prompt, ids, slots.numel())
+
+
+class GuidedState:
+    """The automaton state of every running guided sequence: one int32 per slot, on the engine's
+    device (a CPU tensor for the CPU engine).  The sampling launch reads a row's state to mask
+    the logits and stores the successor after the draw, so guided requests keep async
+    scheduling.  Allocated at the first guided request; slots are handed out and returned like
+    ``SamplerState``'s (stream order makes the reuse safe: the next owner's state is written by
+    a copy enqueued after every launch that could still advance the old owner's)."""
+
+    def __init__(self, num_slots: int, device: torch.device):
+        self.num_slots, self.device = num_slots, device
+        self.state: Optional[torch.Tensor] = None
+        self.free: List[int] = list(range(num_slots - 1, -1, -1))
+
+    @property
+    def num_free(self) -> int:
+        return len(self.free)
+
+    def acquire(self) -> int:
+        if self.state is None:
+            self.state = torch.zeros(self.num_slots, dtype=torch.int32, device=self.device)
+        return self.free.pop()
+
+    def release(self, seq) -> None:
+        if seq.guided_slot >= 0:
+            self.free.append(seq.guided_slot)
+            seq.guided_slot = -1
+        if seq.guided_table is not None and seq.finished:
+            seq.guided_table.refs -= 1
+            seq.guided_table = None
+
+    def write(self, slots: torch.Tensor, states: torch.Tensor) -> None:
+        """int64 slots [n] and int32 states [n] on the device: the newly admitted sequences."""
+        self.state.index_copy_(0, slots, states)
+
+
+def advance_guided_ref(state: torch.Tensor, tables, slots, tokens) -> None:
+    """Torch reference of the kernel's state update: state[slot] = next[state][token] when that
+    is >= 0.  ``tables``: the row's token table tensor or None."""
+    for i, nx in enumerate(tables):
+        if nx is None:
+            continue
+        n = int(nx[int(state[slots[i]]), int(tokens[i])])
+        if n >= 0:
+            state[slots[i]] = n
 
 
 def counts_from_ids(prompt_ids, output_ids, vocab: int) -> torch.Tensor:

@@ -36,6 +36,11 @@ class SamplingParams:
     min_p: float = 0.0
     logit_bias: Optional[Dict[int, float]] = None
     min_tokens: int = 0
+    # guided decoding (lumen/serve/guided.py): (kind, canonical payload) with kind "regex",
+    # "choice" or "json"; the output is a full match of the grammar followed by EOS.
+    # guided_dfa: the compiled (trans, accept) when the API process has compiled it already
+    guided: Optional[Tuple[str, str]] = None
+    guided_dfa: Optional[tuple] = None
 
     @property
     def has_penalties(self) -> bool:
@@ -71,13 +76,30 @@ class SamplingParams:
             if any(k < 0 for k in bias) or not all(-100.0 <= v <= 100.0 for v in bias.values()):
                 raise ValueError("logit_bias ids must be >= 0 and its values in [-100, 100]")
             self.logit_bias = bias or None
+        if self.guided is not None:
+            g = self.guided
+            if isinstance(g, dict):
+                # the request's spelling: {"regex": ...} | {"choice": [...]} | {"json": schema}
+                if len(g) != 1:
+                    raise ValueError("only one of guided regex, choice and json may be given")
+                from .guided import canonical
+                (kind, value), = g.items()
+                g = (kind, canonical(kind, value))
+            if (not isinstance(g, (tuple, list)) or len(g) != 2
+                    or g[0] not in ("regex", "choice", "json") or not isinstance(g[1], str)):
+                raise ValueError("guided must be (kind, payload) with kind regex, choice or json")
+            self.guided = (g[0], g[1])
+            if self.min_tokens > 0:
+                raise ValueError("guided decoding cannot be combined with min_tokens: the "
+                                 "grammar decides when EOS is legal")
 
     @property
     def row_features(self) -> bool:
         """Anything the per-row sampler entry serves beyond temperature / top-k / top-p (the
         penalties count only where the engine keeps their state on the device)."""
         return ((self.seed is not None and self.temperature > 0) or self.min_p > 0.0
-                or self.logit_bias is not None or self.min_tokens > 0)
+                or self.logit_bias is not None or self.min_tokens > 0
+                or self.guided is not None)
 
     @property
     def wants_extras(self) -> bool:
@@ -130,6 +152,10 @@ class Sequence:
     ngram_upto: int = 0
     state_slot: int = -1         # row of the device sampler state (penalty counts); -1: none
     bias_np: Optional[tuple] = field(default=None, repr=False)   # logit_bias as (ids, values)
+    # guided decoding: the grammar's token table (guided.TokenTable, held while the sequence is
+    # alive) and the row of the device automaton state; -1: none
+    guided_table: Optional[object] = field(default=None, repr=False)
+    guided_slot: int = -1
 
     @property
     def all_ids(self) -> List[int]:
